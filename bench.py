@@ -24,7 +24,8 @@ in `c5`: 8192x28672 W4 g128, M = 4096, N/world column shards (strong scaling), t
 GEMM by M-tiles (bitorch_engine.distributed; timed by bench_sharded.bench_column_sharded).  `--dry-run --backend gloo` rehearses the
 launcher, the rendezvous and the timed-region protocol on the CPU (tests/test_bench_launcher_cpu.py); it measures nothing.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the last timed step computed (DIR/y.npy, float32, one row per layer):
+the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -381,6 +382,25 @@ class Bench:
         return {"M": M, "K": k, "N": n, "layers": nl, "us_per_launch": round(us, 2), "GB/s_algorithmic": round(alg_bytes(M, k, n) / us / 1e3, 1),
                 "roofline": {"bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                              "frac": round(tf / MFMA_PEAK_TFLOPS, 4), "traffic": None}}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32, 64 MB in all at most.  An array whose share of the budget is too
+    small for all of it keeps a fixed, seeded sample of its rows (the row indices go beside it as <name>_rows.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share and a.ndim > 1:
+            keep = max(1, (share - 8 * len(a)) // a[0].nbytes)
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def plan_x(plan):
@@ -832,8 +852,9 @@ def main():
     os.environ.setdefault("BIE_TUNING", "1")  # GEMM plan knobs re-read per launch (one getenv each; the timed regions are captured graphs)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="K: timed decode passes per timed region (ms_per_step = region time / K)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed regions, write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline only (used under rocprofv3)")
     ap.add_argument("--only", default="", help="profiling aid: run only this shape's M=1 decode pass, e.g. 4096x11008")
@@ -842,6 +863,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the launcher / rendezvous / timed-region protocol under gloo: no kernel runs, value is null")
     ap.add_argument("--sequential-gather", action="store_true", help="N > 1: all-gather on the compute stream after every pass instead of overlapped under the next pass")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: --dry-run computes nothing to dump")
 
     import bench_sharded as bs
     # The driver's contract names two ways of starting N ranks: `python -m torch.distributed.run ... bench.py --gpus N` (WORLD_SIZE set: this
@@ -929,6 +954,11 @@ def main():
     n_regions = max(1, int(os.environ.get("BIE_BENCH_REGIONS", "5")))
     regions = sorted((timed_region() for _ in range(n_regions)), key=lambda r: r[0])
     elapsed, gpu_ms = regions[len(regions) // 2]
+    # --dump-outputs: what the last timed step handed its caller (the region's closing barrier synchronised the device, the gather's
+    # stream included).  Single GPU: the step's 96 rows of y.  Ranks: the all-gathered rows of the last pass, rank-major.
+    if args.dump_outputs and rank == 0:
+        y_last = gather.gathered.view(world, chunk, LAYERS, N)[:, chunk - 1].reshape(world * LAYERS, N) if distributed else y_all[:LAYERS]
+        dump_outputs(args.dump_outputs, {"y": y_last})
 
     ms_per_step = elapsed / args.steps * 1e3
     step_bytes = alg_bytes(1, K, N) * LAYERS

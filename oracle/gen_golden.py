@@ -209,7 +209,11 @@ def optim_diodemix_vectors():
         g = torch.Generator().manual_seed(600 + len(tag))
         p = torch.nn.Parameter(torch.randn(shape, generator=g))
         out[f"galore_{tag}_0"] = tonp(p).copy()
-        opt = DiodeMix([{"params": [p], "rank": 4, "update_proj_gap": 2, "scale": 0.25, "proj_type": pt}], lr=2e-3, betas=(0.9, 0.99), weight_decay=0.0)
+        # "full" on a refresh step projects G onto its own singular vectors: U^T G V = diag(s) + rounding noise (~1e-7) off the diagonal.
+        # With eps = 1e-6 the first Adam step turns that noise into O(1) updates, i.e. into whatever the CPU's LAPACK path rounded;
+        # eps = 1e-3 keeps the noise out of the step (the diagonal still normalises to ~1), so the vectors hold on any CPU.
+        extra = {"eps": 1e-3} if pt == "full" else {}
+        opt = DiodeMix([{"params": [p], "rank": 4, "update_proj_gap": 2, "scale": 0.25, "proj_type": pt, **extra}], lr=2e-3, betas=(0.9, 0.99), weight_decay=0.0)
         for it in range(1, 5):
             p.grad = torch.randn(shape, generator=g) * 0.1
             out[f"galore_{tag}_grad{it}"] = tonp(p.grad)

@@ -22,6 +22,12 @@ def _free_port():
     return p
 
 
+def _cpu_barrier():
+    """gloo's own barrier.  dist.barrier() first asks torch which accelerator the machine has, and on a GPU machine that question
+    initialises the GPU runtime in every rank: eight CPU-only ranks would hold the GPU open for nothing."""
+    dist.monitored_barrier()
+
+
 def _oracle_impl(x2, qweight, scales, zeros, g_idx, w_bit, asym, group_size, bias):
     from oracle import oracle as orc
     dt = orc.dt_code(x2.dtype)
@@ -99,7 +105,7 @@ def _worker(rank, world, port, asym, out_dir):
                 pass
     ok_direct = ok_direct and torch.equal(layer.forward_direct(x), full)  # leading dims, one tile
     torch.save({"ok": ok and ok_tiled and ok_rm and ok_direct, "shape": tuple(y.shape)}, os.path.join(out_dir, f"r{rank}.pt"))
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -139,7 +145,7 @@ def _worker_c5(rank, world, port, out_dir):
     # every rank took part in every collective: the gathered result holds all eight column blocks, and the world really is 8
     res["world"] = dist.get_world_size() == 8
     torch.save(res, os.path.join(out_dir, f"r{rank}.pt"))
-    dist.barrier()
+    _cpu_barrier()
     dist.destroy_process_group()
 
 

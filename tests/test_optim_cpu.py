@@ -39,10 +39,12 @@ def test_float_parameters_take_the_reference_adamw_steps(vec):
                                            ("rstd_wide", "reverse_std", (20, 48)), ("left", "left", (20, 48)), ("right", "right", (20, 48)), ("full", "full", (20, 48))])
 def test_galore_groups_follow_the_reference(vec, tag, pt, shape):
     """A GaLore group (rank 4, projector refreshed every second step, scale 0.25) of every projection type: the parameter after each of four
-    steps.  The SVD is LAPACK's on both sides; 1e-4 relative leaves room for another CPU's BLAS, a wrong side or a missing scale is off by 1."""
+    steps.  The SVD is LAPACK's on both sides; 1e-4 relative leaves room for another CPU's BLAS, a wrong side or a missing scale is off by 1.
+    "full" runs at eps 1e-3 (oracle/gen_golden.py says why): at 1e-6 its refresh steps amplify LAPACK's rounding into the update."""
     p = torch.nn.Parameter(torch.from_numpy(vec[f"galore_{tag}_0"]).clone())
     assert tuple(p.shape) == shape
-    opt = DiodeMix([{"params": [p], "rank": 4, "update_proj_gap": 2, "scale": 0.25, "proj_type": pt}], lr=2e-3, betas=(0.9, 0.99), weight_decay=0.0)
+    extra = {"eps": 1e-3} if pt == "full" else {}
+    opt = DiodeMix([{"params": [p], "rank": 4, "update_proj_gap": 2, "scale": 0.25, "proj_type": pt, **extra}], lr=2e-3, betas=(0.9, 0.99), weight_decay=0.0)
     for it in range(1, 5):
         p.grad = torch.from_numpy(vec[f"galore_{tag}_grad{it}"]).clone()
         opt.step()
