@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "../../include/bie_hip.h"
 
@@ -31,6 +32,33 @@ int check_launch(const char* what);
             return (code);                \
         }                                 \
     } while (0)
+
+// zero modes of the MPQ weights (the rounding of each is spelled out in mpq_dequant.cuh)
+constexpr int ZM_SYM = 0, ZM_ASYM = 1, ZM_FUSED = 2;
+
+// ---- tuning knobs ---------------------------------------------------------------------------------
+// An unset knob reads as `dflt` (a set but empty one as 0).
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+// BIE_TUNING (tests, sweep tools) is read once per process; under it the knobs read through BIE_KNOB are re-read on every call.
+static inline bool tuning() {
+    static const bool t = getenv("BIE_TUNING") != nullptr;
+    return t;
+}
+// A knob read once per process -- or per call under BIE_TUNING.  No getenv on the launch path otherwise.
+#define BIE_KNOB(name, dflt) \
+    (::bie::tuning() ? ::bie::env_int(name, dflt) : [] { static const int once_ = ::bie::env_int(name, dflt); return once_; }())
+
+// nearest point of an ascending grid in log space (the geometric mean of two neighbours is the boundary); -1 when x is more than
+// 20 % outside the grid.  Looks up the measured tables (mpq_gemm_plan_table.inc, mpq_dense_table.inc).
+static inline int grid_index(const int* g, int n, long x) {
+    if ((double)x * 1.2 < (double)g[0] || (double)x > (double)g[n - 1] * 1.2) return -1;
+    int i = 0;
+    while (i + 1 < n && (double)x * (double)x > (double)g[i] * (double)g[i + 1]) i++;
+    return i;
+}
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -452,14 +452,15 @@ __global__ __launch_bounds__(256) void xnor_mid_kernel(const void* __restrict__ 
     }
 }
 
-static int env_int(const char* name, int dflt) {
+// unlike env_int (bie_common.h), an empty value reads as unset
+static int env_int_nonempty(const char* name, int dflt) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : dflt;
 }
 struct MidPlan { int rt, g; };
 // widest tile whose grid still gives every CU a workgroup; BIE_BINARY_MID=<rt><g> (e.g. 84) pins one for tools/
 static MidPlan mid_plan(long M, long N) {
-    static const int forced = env_int("BIE_BINARY_MID", 0);
+    static const int forced = env_int_nonempty("BIE_BINARY_MID", 0);
     if (forced == 84 || forced == 44 || forced == 42 || forced == 41) return MidPlan{forced / 10, forced % 10};
     // (8 rows with 2 or 1 column groups measured slower than 4 x 4 at equal grid size: profiles/r03_u_binary_mid_ab.txt)
     const int cand[4][2] = {{8, 4}, {4, 4}, {4, 2}, {4, 1}};
@@ -471,7 +472,7 @@ static MidPlan mid_plan(long M, long N) {
 }
 // upper M: beyond it the 128 x 128 register-tile kernel (weights re-read once per 128 rows, not once per RT) wins -- measured crossover
 static long mid_max_rows() {
-    static const int v = env_int("BIE_BINARY_MID_MAX", 512);
+    static const int v = env_int_nonempty("BIE_BINARY_MID_MAX", 512);
     return v;
 }
 bool binary_mid_ok(long M, long N, long K) {

@@ -1,27 +1,15 @@
 // extern "C" surface of libbie_hip.so (see include/bie_hip.h for the contract and the reference
 // functions each entry point replaces).  Argument validation + dispatch only; kernels live in the
 // sibling translation units.
-#include "bie_common.h"
+#include "mpq_plan.h"
 #include <stdlib.h>
 
 namespace bie {
 const char* get_error();
-// mpq_gemv.hip
-bool mpq_gemv_fast_ok(int M, int K, int N, int w_bit, int group_size, int dtype, bool has_gidx);
+// mpq_gemv.hip, mpq_gemv_lut.hip
 size_t mpq_gemv_workspace_bytes(int M, int K, int N, int w_bit);
-int mpq_gemv_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                    float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                    hipStream_t st);
-int mpq_gemv_generic_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx,
-                            const void* bias, void* y, float* part, int M, int K, int N, int w_bit, int group_size,
-                            int asym, int dtype, hipStream_t st, const uint16_t* perm = nullptr);
-// mpq_gemv_lut.hip
-bool mpq_gemv_lut_ok(int M, int K, int w_bit, int group_size, int dtype, bool has_gidx, int N = 0);  // N > 0: a lone call (17 .. 32 rows on measured shapes)
 bool mpq_lut_rb2_grouped_ok(int M, int K, long n_total, int dtype);
-size_t mpq_gemv_lut_part_floats(int M, int K, int group_size, int tiles_total, int w_bit);
-int mpq_gemv_lut_launch(int nsets, const int32_t* const* qw, const void* const* scales, const void* const* zeros,
-                        const void* const* bias, void* const* y, const int* N, const void* x, unsigned* counters, float* part,
-                        int M, int K, int group_size, int zm, int dtype, hipStream_t st, int w_bit);
+size_t mpq_gemv_lut_workspace_bytes(int M, int K, int tiles_total, int w_bit);
 // mpq_list.hip
 struct MpqList;
 size_t mpq_list_device_bytes(int n, const bie_mpq_list_entry* ent, int M, int w_bit, int group_size);
@@ -40,13 +28,7 @@ void test_forge_dep_set(int extra);
 // mpq_gemm.hip
 bool mpq_gemm_ok(int M, int K, int N, int w_bit, int group_size, int dtype, bool has_gidx);
 size_t mpq_gemm_workspace_bytes(int M, int K, int N);
-int mpq_gemm_launch_ld(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                       float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                       hipStream_t st, int ldy);
 bool mpq_gemm_pitch_ok(int M, int K, int N, int ldy);
-int mpq_gemm_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                    float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                    hipStream_t st);
 // mpq_util.hip
 int mpq_dequant_launch(const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx, void* out, int K,
                        int N, int w_bit, int group_size, int asym, int dtype, hipStream_t st);
@@ -57,11 +39,8 @@ int gather_cols_launch(const void* x, const int32_t* perm, void* out, int M, int
 int mpq_grad_input_launch(const void* gy, const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx,
                           void* gx, int M, int K, int N, int w_bit, int group_size, int asym, int dtype, hipStream_t st);
 // mpq_dense.hip
-bool mpq_dense_shape_ok(int K, int N);
 size_t mpq_dense_workspace_bytes(int K, int N);
 bool mpq_dense_ok(int M, int K, int N);
-int mpq_dense_gidx_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx, const void* bias, void* y, void* scratch,
-                          int M, int K, int N, int w_bit, int asym, int dtype, hipStream_t st);
 // mbwq.hip
 size_t mbwq_workspace_bytes(int M, int K, int N, bool exl2);
 int mbwq_q4_dequant_launch(const int32_t* qw, const void* scales, const void* zeros, const int16_t* perm, void* out, int K,
@@ -134,7 +113,6 @@ int q4_conv2d_launch(const int8_t* a_packed, const int8_t* w_packed, void* y, vo
 
 using namespace bie;
 
-static const int GENERIC_M_CHUNK = 32;
 // The first 16 KiB (BIE_WS_HEAD_BYTES) of every workspace hold the GEMV's split-K arrival counters (zero on first use, returned to zero by
 // the kernel); every other scratch user starts behind them.
 static const size_t WS_HEAD = BIE_WS_HEAD_BYTES;
@@ -172,9 +150,6 @@ int bie_mpq_list_launches(const bie_mpq_list_t* plan) { return mpq_list_launches
 int bie_mpq_list_form(const bie_mpq_list_t* plan) { return mpq_list_form(reinterpret_cast<const MpqList*>(plan)); }
 void bie_mpq_list_destroy(bie_mpq_list_t* plan) { mpq_list_destroy(reinterpret_cast<MpqList*>(plan)); }
 
-// explicit g_idx that is not a permutation of k // group_size, prefill: per-k dequantise into the fragment image + the dense GEMM (mpq_dense.hip)
-static bool gidx_dense_ok(int M, int K, int N, int dtype) { return M > 32 && (dtype == BIE_F16 || dtype == BIE_BF16) && mpq_dense_shape_ok(K, N); }
-
 int bie_mpq_prefill_form(int M, int K, int N) { return (M > 32 && mpq_dense_ok(M, K, N)) ? 1 : 0; }
 int bie_mpq_grouped_max_rows(int K, long n_total, int w_bit, int dtype) {
     if (w_bit == 2) return 2;
@@ -182,10 +157,14 @@ int bie_mpq_grouped_max_rows(int K, long n_total, int w_bit, int dtype) {
     return mpq_lut_rb2_grouped_ok(32, K, n_total, dtype) ? 32 : 16;
 }
 int bie_mpq_rows_form(int M, int K, int N, int w_bit, int group_size, int dtype) {
-    static const int lut_max_m = []() { const char* e = getenv("BIE_LUT_MAX_M"); return e ? atoi(e) : 16; }();
     if (M <= 0 || K <= 0 || N <= 0) return 0;
-    if (M <= (lut_max_m >= 16 ? 32 : lut_max_m) && cdiv(N, 64) <= BIE_WS_COUNTERS && (N & 3) == 0 && mpq_gemv_lut_ok(M, K, w_bit, group_size, dtype, false, N)) return 2;
+    if (mpq_decode_first(M, K, N, w_bit, group_size, dtype)) return 2;
     return bie_mpq_prefill_form(M, K, N);
+}
+int bie_test_mpq_forward_plan(int M, int K, int N, int w_bit, int group_size, int dtype, int has_gidx, size_t workspace_bytes, size_t* need) {
+    const MpqPlan p = mpq_forward_plan(M, K, N, w_bit, group_size, ZM_SYM, dtype, has_gidx != 0, false, workspace_bytes, mpq_lut_first_rows(), mpq_gemv_max_m());
+    if (need) *need = p.workspace_bytes;
+    return (int)p.form;
 }
 size_t bie_mpq_workspace_bytes_gidx(int M, int K, int N, int w_bit) {
     const size_t base = bie_mpq_workspace_bytes(M, K, N, w_bit);
@@ -194,6 +173,7 @@ size_t bie_mpq_workspace_bytes_gidx(int M, int K, int N, int w_bit) {
     return img > base ? img : base;
 }
 
+// covers mpq_forward_plan(...).workspace_bytes of every call of these sizes without g_idx, whatever its dtype and group size (tests/test_boundary_cpu.py)
 size_t bie_mpq_workspace_bytes(int M, int K, int N, int w_bit) {
     if (M <= 0 || K <= 0 || N <= 0 || !(w_bit == 1 || w_bit == 2 || w_bit == 4 || w_bit == 8)) return 0;
     size_t a = M <= 32 ? mpq_gemv_workspace_bytes(M, K, N, w_bit) : 0;
@@ -218,36 +198,9 @@ int bie_mpq_forward(const void* x, const int32_t* qweight, const void* scales, c
                 "bie_mpq_forward: workspace of %zu bytes required, got %zu", need, workspace_bytes);
     rc = status_report("bie_mpq_forward");
     if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    float* head = reinterpret_cast<float*>(workspace);
-    float* part = head + WS_HEAD / sizeof(float);
-    const bool has_gidx = g_idx != nullptr;
-    // M <= 2: the dot2 GEMV; 3 <= M: the MFMA kernel (its dequant cost does not grow with M; measured faster from M = 3).
-    // The GEMV also serves M <= 8 for shapes the MFMA tiling cannot take.
-    const bool gemm_ok = mpq_gemm_ok(M, K, N, w_bit, group_size, dtype, has_gidx);
-    static const int gemv_max_m = []() { const char* e = getenv("BIE_GEMV_MAX_M"); return e ? atoi(e) : 2; }();  // tuning knob
-    // W4 decode and small batches: the table-lookup kernels (mpq_gemv_lut_ok says which M each form takes)
-    static const int lut_max_m = []() { const char* e = getenv("BIE_LUT_MAX_M"); return e ? atoi(e) : 16; }();
-    if (M <= (lut_max_m >= 16 ? 32 : lut_max_m) && cdiv(N, 64) <= BIE_WS_COUNTERS && (N & 3) == 0 && mpq_gemv_lut_ok(M, K, w_bit, group_size, dtype, has_gidx, N))
-        return mpq_gemv_launch(x, qweight, scales, zeros, bias, y, head, M, K, N, w_bit, group_size, asym ? 1 : 0, dtype, nullptr, st);
-    if (M <= 8 && (M <= gemv_max_m || !gemm_ok) && mpq_gemv_fast_ok(M, K, N, w_bit, group_size, dtype, has_gidx))
-        return mpq_gemv_launch(x, qweight, scales, zeros, bias, y, head, M, K, N, w_bit, group_size, asym ? 1 : 0, dtype, nullptr, st);
-    if (gemm_ok)
-        return mpq_gemm_launch(x, qweight, scales, zeros, bias, y, part, M, K, N, w_bit, group_size, asym ? 1 : 0, dtype, nullptr, st);
-    // explicit irregular g_idx, prefill: the reference materialises the dense weight and calls cuBLAS (mpq_layer.py:59-63); here the
-    // per-k dequantise writes the MFMA fragment image and the dense kernel multiplies -- when the caller sized the workspace for it
-    // (bie_mpq_workspace_bytes_gidx); a smaller workspace keeps the generic kernel below
-    if (has_gidx && gidx_dense_ok(M, K, N, dtype) && workspace_bytes >= WS_HEAD + mpq_dense_workspace_bytes(K, N))
-        return mpq_dense_gidx_launch(x, qweight, scales, zeros, g_idx, bias, y, part, M, K, N, w_bit, asym ? 1 : 0, dtype, st);
-    // generic path (explicit g_idx / odd shapes / fp32), GENERIC_M_CHUNK rows at a time
-    const size_t esz = dtype == BIE_F32 ? 4 : 2;
-    for (int m0 = 0; m0 < M; m0 += GENERIC_M_CHUNK) {
-        const int mc = (M - m0) < GENERIC_M_CHUNK ? (M - m0) : GENERIC_M_CHUNK;
-        rc = mpq_gemv_generic_launch((const char*)x + (size_t)m0 * K * esz, qweight, scales, zeros, g_idx, bias,
-                                     (char*)y + (size_t)m0 * N * esz, part, mc, K, N, w_bit, group_size, asym, dtype, st);
-        if (rc) return rc;
-    }
-    return BIE_OK;
+    const int zm = asym ? ZM_ASYM : ZM_SYM;
+    const MpqPlan p = mpq_forward_plan(M, K, N, w_bit, group_size, zm, dtype, g_idx != nullptr, false, workspace_bytes, mpq_lut_first_rows(), mpq_gemv_max_m());
+    return mpq_forward_launch(p.form, x, qweight, scales, zeros, g_idx, nullptr, bias, y, workspace, M, K, N, w_bit, group_size, zm, dtype, as_stream(stream));
 }
 
 // y is a column range of a wider row-major destination: row m of the result goes to y + m * ldy (elements).  Served by the MFMA GEMM range
@@ -261,7 +214,7 @@ int bie_mpq_forward_pitched(const void* x, const int32_t* qweight, const void* s
     if (rc) return rc;
     BIE_REQUIRE(x && qweight && scales && zeros && y && M > 0, BIE_ERR_INVALID_ARG, "bie_mpq_forward_pitched: bad argument");
     if (asym) BIE_REQUIRE(N % (32 / w_bit) == 0, BIE_ERR_INVALID_ARG, "bie_mpq_forward_pitched: asym needs N %% %d == 0", 32 / w_bit);
-    static const int lut_max_m = []() { const char* e = getenv("BIE_LUT_MAX_M"); return e ? atoi(e) : 16; }();
+    const int lut_max_m = mpq_lut_max_m();
     BIE_REQUIRE(M > lut_max_m && M > 8 && mpq_gemm_ok(M, K, N, w_bit, group_size, dtype, false) && mpq_gemm_pitch_ok(M, K, N, ldy) &&
                     (reinterpret_cast<uintptr_t>(y) & 7) == 0,
                 BIE_ERR_UNSUPPORTED, "bie_mpq_forward_pitched: M=%d K=%d N=%d ldy=%d is outside the range of the MFMA GEMM's pitched epilogue (M > %d, ldy %% 4 == 0, ldy >= N, no split-K plan, y 8-byte aligned)",
@@ -271,7 +224,9 @@ int bie_mpq_forward_pitched(const void* x, const int32_t* qweight, const void* s
     rc = status_report("bie_mpq_forward_pitched");
     if (rc) return rc;
     float* part = reinterpret_cast<float*>(workspace) + WS_HEAD / sizeof(float);
-    return mpq_gemm_launch_ld(x, qweight, scales, zeros, bias, y, part, M, K, N, w_bit, group_size, asym ? 1 : 0, dtype, nullptr, as_stream(stream), ldy);
+    const int zm = asym ? ZM_ASYM : ZM_SYM;
+    return mpq_gemm_launch_ld(mpq_gemm_form(M, K, N, zm, dtype, false), x, qweight, scales, zeros, bias, y, part, M, K, N, w_bit, group_size, zm, dtype, nullptr,
+                              as_stream(stream), ldy);
 }
 
 int bie_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
@@ -294,15 +249,8 @@ size_t bie_mpq_grouped_workspace_bytes(int n_sets, const int* N, int M, int K, i
         const size_t b = bie_mpq_workspace_bytes(M, K, N[i], w_bit);
         if (b > need) need = b;
     }
-    if ((w_bit == 4 && M <= 32) || (w_bit == 2 && M <= 2)) {  // 17 .. 32 rows: the two-row-block instance (taken on measured sets only, sized always)
-        const int tiles = grouped_tiles(n_sets, N);
-        for (int gs = 32; gs <= 256; gs *= 2)
-            if (K % gs == 0) {
-                const size_t b = WS_HEAD + mpq_gemv_lut_part_floats(M, K, gs, tiles, w_bit) * sizeof(float);
-                if (b > need) need = b;
-            }
-    }
-    return need;
+    const size_t lut = mpq_gemv_lut_workspace_bytes(M, K, grouped_tiles(n_sets, N), w_bit);  // 17 .. 32 rows: the two-row-block instance (taken on measured sets only, sized always)
+    return lut > need ? lut : need;
 }
 
 int bie_mpq_forward_grouped(const void* x, int n_sets, const int32_t* const* qweight, const void* const* scales,
@@ -323,17 +271,12 @@ int bie_mpq_forward_grouped(const void* x, int n_sets, const int32_t* const* qwe
                 "bie_mpq_forward_grouped: workspace of %zu bytes required, got %zu", need, workspace_bytes);
     int src = status_report("bie_mpq_forward_grouped");
     if (src) return src;
-    const int tiles = grouped_tiles(n_sets, N);
-    bool n4 = true;  // the matrix-pipe form loads four adjacent columns with one 16-byte load
-    for (int i = 0; i < n_sets; i++) n4 = n4 && (N[i] & 3) == 0;
-    long n_total = 0;
-    for (int i = 0; i < n_sets; i++) n_total += N[i];
-    // 17 .. 32 rows: the two-row-block instance where it measured ahead of the members' own calls (mpq_lut_rb2_grouped_ok); the shape checks are those of a 16-row call
-    const bool rb2 = w_bit == 4 && M > 16 && M <= 32 && n_sets > 1 && mpq_lut_rb2_grouped_ok(M, K, n_total, dtype) && mpq_gemv_lut_ok(16, K, w_bit, group_size, dtype, false);
-    if (n4 && tiles <= BIE_WS_COUNTERS && (rb2 || mpq_gemv_lut_ok(M, K, w_bit, group_size, dtype, false))) {
+    const int zm = asym ? ZM_ASYM : ZM_SYM;
+    const MpqForm form = mpq_grouped_form(n_sets, N, M, K, w_bit, group_size, zm, dtype);
+    if (form == MpqForm::Lut || form == MpqForm::InlineList) {
         float* head = reinterpret_cast<float*>(workspace);
-        return mpq_gemv_lut_launch(n_sets, qweight, scales, zeros, bias, y, N, x, reinterpret_cast<unsigned*>(head) + BIE_WS_GEN_OFFSET,
-                                   head + WS_HEAD / sizeof(float), M, K, group_size, asym ? 1 : 0, dtype, as_stream(stream), w_bit);
+        return mpq_gemv_lut_launch(form, n_sets, qweight, scales, zeros, bias, y, N, x, reinterpret_cast<unsigned*>(head) + BIE_WS_GEN_OFFSET,
+                                   head + WS_HEAD / sizeof(float), M, K, group_size, zm, dtype, as_stream(stream), w_bit);
     }
     for (int i = 0; i < n_sets; i++) {  // every other case: one launch per set (same results)
         int rc = bie_mpq_forward(x, qweight[i], scales[i], zeros[i], nullptr, bias ? bias[i] : nullptr, y[i], workspace,

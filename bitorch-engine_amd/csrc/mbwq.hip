@@ -15,7 +15,7 @@
 //       - 3 <= M <= 64: exl2_mfma_kernel (per-weight fp16 fma dequant == the reference's __hfma2, LDS transpose into
 //         v_mfma_f32_16x16x32_f16); beyond: the Python front-end reconstructs + library GEMM like the reference;
 //       - reconstruction (exl2_dequant_kernel): the reference's single-rounding __hfma2, bit-exact.
-#include "bie_common.h"
+#include "mpq_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -26,15 +26,7 @@ namespace bie {
 unsigned* device_status_word();                            // splitk.hip
 void test_forge_get(unsigned* tag_skew, int* spin_limit);  // splitk.hip
 
-int mpq_gemv_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                    float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                    hipStream_t st);
-bool mpq_gemv_fast_ok(int M, int K, int N, int w_bit, int group_size, int dtype, bool has_gidx);
 size_t mpq_gemv_workspace_bytes(int M, int K, int N, int w_bit);
-int mpq_gemm_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                    float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                    hipStream_t st);
-bool mpq_gemm_ok(int M, int K, int N, int w_bit, int group_size, int dtype, bool has_gidx);
 int mpq_gemv_generic_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx, const void* bias, void* y, float* part,
                             int M, int K, int N, int w_bit, int group_size, int asym, int dtype, hipStream_t st, const uint16_t* perm);
 constexpr int MBWQ_GENERIC_M_CHUNK = 32;  // rows per launch of the any-shape kernel (its partial sums: cdiv(K, 512) x rows x N floats)
@@ -1571,24 +1563,13 @@ int mbwq_exl2_dequant_launch(const int32_t* qw, const void* scales, const void* 
 
 int mbwq_q4_forward_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const int16_t* perm,
                            void* y, float* part, int M, int K, int N, int bits, int group_size, hipStream_t st) {
-    const uint16_t* p = (const uint16_t*)perm;
-    const bool gemm_ok = mpq_gemm_ok(M, K, N, bits, group_size, BIE_F16, false);
-    if (M <= 8 && (M <= 2 || !gemm_ok) && mpq_gemv_fast_ok(M, K, N, bits, group_size, BIE_F16, false))
-        return mpq_gemv_launch(x, qw, scales, zeros, nullptr, y, part, M, K, N, bits, group_size, 2, BIE_F16, p, st);
-    if (gemm_ok)
-        return mpq_gemm_launch(x, qw, scales, zeros, nullptr, y, part + BIE_WS_HEAD_BYTES / sizeof(float), M, K, N, bits, group_size, 2, BIE_F16, p, st);
-    // any other shape the layout itself allows (whole packed words: K a multiple of 32 / bits; whole groups): the one-column-per-lane kernel with the
-    // same per-weight rounding, 32 rows per launch.  The reference takes such shapes too (its kernels bound-check K and N,
+    // the MPQ plan with the fused rounding: the GEMV up to 2 rows (the decode kernels as its form when there is no perm), the MFMA GEMM
+    // beyond; any other shape the layout itself allows (whole packed words: K a multiple of 32 / bits; whole groups) takes the one-column-per-lane
+    // kernel with the same per-weight rounding.  The reference takes such shapes too (its kernels bound-check K and N,
     // mbwq_linear_cuda_kernel.cu:740-830); this used to be a refusal (found by tests/sweeps/fuzz_other_ops.py).  A correctness path, not a fast one.
-    if (K % (32 / bits) == 0 && (group_size >= K || K % group_size == 0)) {
-        for (int m0 = 0; m0 < M; m0 += MBWQ_GENERIC_M_CHUNK) {
-            const int mc = (M - m0) < MBWQ_GENERIC_M_CHUNK ? (M - m0) : MBWQ_GENERIC_M_CHUNK;
-            const int rc = mpq_gemv_generic_launch((const uint16_t*)x + (size_t)m0 * K, qw, scales, zeros, nullptr, nullptr, (uint16_t*)y + (size_t)m0 * N,
-                                                   part + BIE_WS_HEAD_BYTES / sizeof(float), mc, K, N, bits, group_size, 2, BIE_F16, st, p);
-            if (rc) return rc;
-        }
-        return BIE_OK;
-    }
+    const MpqForm form = mpq_forward_plan(M, K, N, bits, group_size, ZM_FUSED, BIE_F16, false, perm != nullptr, 0, 0, 2).form;
+    if (form != MpqForm::Generic || (K % (32 / bits) == 0 && (group_size >= K || K % group_size == 0)))
+        return mpq_forward_launch(form, x, qw, scales, zeros, nullptr, (const uint16_t*)perm, nullptr, y, part, M, K, N, bits, group_size, ZM_FUSED, BIE_F16, st);
     set_error("bie_mbwq_q4_forward: unsupported shape M=%d K=%d N=%d bits=%d group_size=%d (K must hold whole packed words and whole groups)", M,
               K, N, bits, group_size);
     return BIE_ERR_UNSUPPORTED;

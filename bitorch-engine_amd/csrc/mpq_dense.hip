@@ -415,11 +415,6 @@ __global__ __launch_bounds__(256) void mpq_dense_gemm_kernel(const uint16_t* __r
 }
 
 // ---- launch plumbing ---------------------------------------------------------------------------------------------------
-static int env_int_dense(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // When: measured against the fused kernel on one box (profiles/r03_dense_ab.txt, r03_dense_k_slope.txt), both forms run the same
 // 0.93 us per 32 MFMAs per wave with every CU busy (0.62 is the bare bf16 MFMA stream at that load's clock: moving a stage's 32 KiB
 // into LDS and 64 KiB out of it costs the same 0.3 us whether the weights arrive dequantised or are dequantised beside the MFMAs).
@@ -430,18 +425,8 @@ static int env_int_dense(const char* name, int dflt) {
 // Depends on (M, K, N) and the process environment only: bie_mpq_workspace_bytes has to reproduce the choice.
 #include "mpq_dense_table.inc"
 
-// nearest grid point in log space (the geometric mean of two neighbours is the boundary); -1 when x is more than 20 % outside the grid
-static int dense_grid_index(const int* g, int n, long x) {
-    if ((double)x * 1.2 < (double)g[0] || (double)x > (double)g[n - 1] * 1.2) return -1;
-    int i = 0;
-    while (i + 1 < n && (double)x * (double)x > (double)g[i] * (double)g[i + 1]) i++;
-    return i;
-}
-
 bool mpq_dense_ok(int M, int K, int N) {
-    static const bool tuning = getenv("BIE_TUNING") != nullptr;
-    static const int on_once = env_int_dense("BIE_GEMM_DENSE", 1), min_once = env_int_dense("BIE_GEMM_DENSE_MIN_M", 897);
-    const int on = tuning ? env_int_dense("BIE_GEMM_DENSE", 1) : on_once, min_m = tuning ? env_int_dense("BIE_GEMM_DENSE_MIN_M", 897) : min_once;
+    const int on = BIE_KNOB("BIE_GEMM_DENSE", 1), min_m = BIE_KNOB("BIE_GEMM_DENSE_MIN_M", 897);
     if (!on || (K & 31) || (N & 7)) return false;
     if (on == 2) return true;  // forced (tests: every shape the kernels can take)
     // profiles/r03_dense_ab4_gm4.txt (dense / fused time, 7 layer shapes x M = 512 .. 8192, tiles walked gm = 4 rows deep per XCD run): with
@@ -451,9 +436,8 @@ bool mpq_dense_ok(int M, int K, int N) {
     // Round 6: inside the measured grid (70 layer shapes x 6 row counts, fused against dense on one box: profiles/r06_dense_rule_sweep.txt) the answer is the
     // measurement at the nearest grid point -- the analytic rule below left 1.9 % on the table on average (77 of 420 cells more than 4 % off, up to 28 %: it
     // knew Llama-7B's shapes only); BIE_GEMM_DENSE_TABLE=0 switches the table off.  Outside the grid (M > 4915, K or N beyond 20 % of it) the rule answers.
-    static const int table_once = env_int_dense("BIE_GEMM_DENSE_TABLE", 1);
-    if ((tuning ? env_int_dense("BIE_GEMM_DENSE_TABLE", 1) : table_once) && M >= min_m) {
-        const int ki = dense_grid_index(kDenseK, 8, K), ni = dense_grid_index(kDenseN, 9, N), mi = dense_grid_index(kDenseM, 6, M);
+    if (BIE_KNOB("BIE_GEMM_DENSE_TABLE", 1) && M >= min_m) {
+        const int ki = grid_index(kDenseK, 8, K), ni = grid_index(kDenseN, 9, N), mi = grid_index(kDenseM, 6, M);
         if (ki >= 0 && ni >= 0 && mi >= 0) return (kDenseTable[ki][ni] >> mi) & 1;
     }
     const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
@@ -473,7 +457,7 @@ static void dequant_frag_launch(const int32_t* qw, const void* scales, const voi
     const long nfrag = (long)cdiv(N, 32) * KS;
     // fragments per wave: W4 takes 2 (four times the waves of the 8-fragment form -- two residency rounds, the store stream of the first under the
     // loads of the second: 0.5-0.8 % of the whole M = 4096 call on every shape, profiles/r06_dq_fpw_ab.txt); BIE_DQ_FPW = 8 | 4 | 1 for the A/B
-    static const int fpw_knob = env_int_dense("BIE_DQ_FPW", 2);
+    static const int fpw_knob = env_int("BIE_DQ_FPW", 2);
     int fpw = (KS & 7) == 0 ? 8 : 1;
     if (fpw == 8 && w_bit == 4 && (fpw_knob == 1 || fpw_knob == 2 || fpw_knob == 4)) fpw = fpw_knob;
     const dim3 grid((unsigned)cdivl(nfrag / fpw, 4));
@@ -516,10 +500,8 @@ static void dense_gemm_launch(const void* x, const void* img, const void* bias, 
         return;
     }
     const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
-    static const int tile_once = env_int_dense("BIE_GEMM_DENSE_TILE", 0), gm_once = env_int_dense("BIE_GEMM_DENSE_GM", 4);
-    const bool tuning = getenv("BIE_TUNING") != nullptr;
-    const int tile = tuning ? env_int_dense("BIE_GEMM_DENSE_TILE", 0) : tile_once;
-    int gm = tuning ? env_int_dense("BIE_GEMM_DENSE_GM", 4) : gm_once;  // tile rows an XCD's run walks down before moving one tile column on
+    const int tile = BIE_KNOB("BIE_GEMM_DENSE_TILE", 0);
+    int gm = BIE_KNOB("BIE_GEMM_DENSE_GM", 4);  // tile rows an XCD's run walks down before moving one tile column on
     if (gm < 1) gm = 1;
     if (tile == 256 || (tile != 128 && t256 >= 192)) {
         const int tn = cdiv(N, 256);

@@ -25,7 +25,7 @@
 
 namespace bie {
 
-constexpr int ZM_SYM = 0, ZM_ASYM = 1, ZM_FUSED = 2;
+// the zero modes ZM_SYM / ZM_ASYM / ZM_FUSED: bie_common.h
 
 // k offset (0..NB-1) of the 16-bit slot `p` (0..NB-1) in pair order
 template <int DT, int WBIT>

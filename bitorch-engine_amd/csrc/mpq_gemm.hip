@@ -20,6 +20,7 @@
 //   * tile height and split-K factor from a measured cost model (plan_gemm); partials reduced in fixed order by
 //     splitk_finalize (an in-kernel ticketed reduction was measured 5-8x slower at GEMM partial volumes).
 #include "mpq_frag_dequant.cuh"
+#include "mpq_plan.h"
 #ifndef BIE_GEMM_LAB
 #define BIE_GEMM_LAB 0  // compile-time ablation switch used by tools/ (0 = product code)
 #endif
@@ -509,11 +510,6 @@ struct GemmPlan {
     int BM, S, tiles_per_split;
 };
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // Tile height and split-K factor from a measured cost model (tools/gemm_plan_sweep2.py,
 // profiles/r01_g_gemm_plan_sweep_after_glds.log).  A K tile (64 k) of a BM x 256 block tile costs c0(BM) us on an otherwise
 // idle chip (the dequant of the 256 columns is paid per tile whatever BM is, hence the weak dependence on BM) and up to
@@ -523,28 +519,15 @@ static int env_int(const char* name, int dflt) {
 // without knowing dtype or bit width.
 #include "mpq_gemm_plan_table.inc"
 
-// nearest grid point in log space; -1 when x is more than 20 % outside the grid
-static int plan_grid_index(const int* g, int n, long x) {
-    if ((double)x * 1.2 < (double)g[0] || (double)x > (double)g[n - 1] * 1.2) return -1;
-    int i = 0;
-    while (i + 1 < n && (double)x * (double)x > (double)g[i] * (double)g[i + 1]) i++;
-    return i;
-}
-
 static GemmPlan plan_gemm(int M, int K, int N) {
-    // tuning knobs: read ONCE per process -- unless BIE_TUNING is set (tests / sweep tools change them between calls), in which
-    // case they are re-read on every launch.  No getenv on the product's launch path.
-    static const bool tuning = getenv("BIE_TUNING") != nullptr;
-    static const int bm_once = env_int("BIE_GEMM_BM", 0), s_once = env_int("BIE_GEMM_S", 0);
-    const int force_bm = tuning ? env_int("BIE_GEMM_BM", 0) : bm_once, force_s = tuning ? env_int("BIE_GEMM_S", 0) : s_once;
+    const int force_bm = BIE_KNOB("BIE_GEMM_BM", 0), force_s = BIE_KNOB("BIE_GEMM_S", 0);  // tuning knobs (tests / sweep tools)
     const int T = K / GEMM_BK;
     // Round 6: where a sweep of EVERY (BM, S) over 40 layer shapes x 11 row counts found a plan more than 2 % ahead of this model's choice
     // (114 of 440 cells, up to 24 %: profiles/r06_gemm_plan_table_sweep.txt -> mpq_gemm_plan_table.inc), the grid point's plan is taken for the grid's own (K, N) and the
     // row counts around its M that make the same number of row tiles.  BIE_GEMM_PLAN_TABLE=0: the model alone.
-    static const int table_once = env_int("BIE_GEMM_PLAN_TABLE", 1);
-    if (!force_bm && !force_s && (tuning ? env_int("BIE_GEMM_PLAN_TABLE", 1) : table_once)) {
-        const int ki = plan_grid_index(kPlanK, (int)(sizeof(kPlanK) / sizeof(int)), K), ni = plan_grid_index(kPlanN, (int)(sizeof(kPlanN) / sizeof(int)), N),
-                  mi = plan_grid_index(kPlanM, (int)(sizeof(kPlanM) / sizeof(int)), M);
+    if (!force_bm && !force_s && BIE_KNOB("BIE_GEMM_PLAN_TABLE", 1)) {
+        const int ki = grid_index(kPlanK, (int)(sizeof(kPlanK) / sizeof(int)), K), ni = grid_index(kPlanN, (int)(sizeof(kPlanN) / sizeof(int)), N),
+                  mi = grid_index(kPlanM, (int)(sizeof(kPlanM) / sizeof(int)), M);
         if (ki >= 0 && ni >= 0 && mi >= 0) {
             const unsigned e = kPlanTable[ki][ni][mi];
             const int BM = 32 << (e >> 5), S = (int)(e & 31u);
@@ -605,6 +588,12 @@ size_t mpq_dense_workspace_bytes(int K, int N);
 int mpq_dense_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y, void* scratch, int M, int K, int N,
                      int w_bit, int gshift, int zm, int dtype, hipStream_t st, int ldy);
 
+// the workspace of one launch of the form (dense or fused), head included
+size_t mpq_gemm_form_bytes(bool dense, int M, int K, int N) {
+    const GemmPlan p = plan_gemm(M, K, N);
+    return BIE_WS_HEAD_BYTES + (dense ? mpq_dense_workspace_bytes(K, N) : (p.S > 1 ? (size_t)p.S * M * N * sizeof(float) : 0));
+}
+
 size_t mpq_gemm_workspace_bytes(int M, int K, int N) {
     if (K % GEMM_BK) return 0;
     const GemmPlan p = plan_gemm(M, K, N);
@@ -655,20 +644,13 @@ static int gemm_launch_mpq_w(const GemmPlan& p, const GemmArgs& a, int w_bit, bo
     }
 }
 
-// ldy: the row pitch of y in elements (N for a tight [M, N]; a wider destination lets a column shard's epilogue store straight into
-// its column range of the full output -- SURVEY section 8e).  The split-K finalize pass writes tight rows only.
-int mpq_gemm_launch_ld(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                       float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                       hipStream_t st, int ldy);
-int mpq_gemm_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
-                    float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
-                    hipStream_t st) {
-    return mpq_gemm_launch_ld(x, qw, scales, zeros, bias, y, part, M, K, N, w_bit, group_size, zm, dtype, perm, st, N);
-}
 bool mpq_gemm_pitch_ok(int M, int K, int N, int ldy) {  // a pitched destination: 8-byte stores need ldy % 4 == 0, and no split-K finalize pass
     return ldy >= N && (ldy & 3) == 0 && (ldy == N || plan_gemm(M, K, N).S == 1 || mpq_dense_ok(M, K, N));
 }
-int mpq_gemm_launch_ld(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
+// form: MpqForm::GemmDense (large M: dequantise once into `part`, dense MFMA GEMM) or MpqForm::GemmFused.
+// ldy: the row pitch of y in elements (N for a tight [M, N]; a wider destination lets a column shard's epilogue store straight into
+// its column range of the full output -- SURVEY section 8e).  The split-K finalize pass writes tight rows only.
+int mpq_gemm_launch_ld(MpqForm form, const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
                        float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
                        hipStream_t st, int ldy) {
     const GemmPlan p = plan_gemm(M, K, N);
@@ -679,7 +661,7 @@ int mpq_gemm_launch_ld(const void* x, const int32_t* qw, const void* scales, con
         while ((1 << gshift) < group_size) gshift++;
         gpt = (group_size % GEMM_BK) == 0;
     }
-    if (!perm && mpq_dense_ok(M, K, N) && (zm != ZM_FUSED || dtype == BIE_F16))  // large M: dequantise once into `part`, dense MFMA GEMM
+    if (form == MpqForm::GemmDense)
         return mpq_dense_launch(x, qw, scales, zeros, bias, y, part, M, K, N, w_bit, gshift, zm, dtype, st, ldy);
     if (ldy != N && p.S > 1) {
         set_error("mpq_gemm_launch: a pitched destination (ldy=%d, N=%d) is not served by the split-K plan of this shape", ldy, N);

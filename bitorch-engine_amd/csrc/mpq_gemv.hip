@@ -21,17 +21,7 @@
 
 namespace bie {
 
-// mpq_gemv_lut.hip
-bool mpq_gemv_lut_ok(int M, int K, int w_bit, int group_size, int dtype, bool has_gidx, int N = 0);  // N > 0: a lone call (17 .. 32 rows on measured shapes)
-size_t mpq_gemv_lut_part_floats(int M, int K, int group_size, int tiles_total, int w_bit);
-int mpq_gemv_lut_launch(int nsets, const int32_t* const* qw, const void* const* scales, const void* const* zeros,
-                        const void* const* bias, void* const* y, const int* N, const void* x, unsigned* counters, float* part,
-                        int M, int K, int group_size, int zm, int dtype, hipStream_t st, int w_bit);
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
+size_t mpq_gemv_lut_workspace_bytes(int M, int K, int tiles_total, int w_bit);  // mpq_gemv_lut.hip
 
 constexpr int GEMV_THREADS = 256;
 constexpr int GEMV_COLS = 256;  // columns per block: 64 lanes x 4
@@ -543,7 +533,7 @@ static GemvPlan plan_gemv(int K, int N, int w_bit, int group_size, int MT) {
     while (U > 1 && (rows_per_group % U) != 0) U >>= 1;
     const int unit = 32;
     const int tiles_n = cdiv(N, GEMV_COLS);
-    static const int target = []() { const char* e = getenv("BIE_GEMV_TARGET_BLOCKS"); return e ? atoi(e) : 1024; }();
+    static const int target = env_int("BIE_GEMV_TARGET_BLOCKS", 1024);
     int S = cdiv(target, tiles_n);  // aim at ~4 blocks per CU
     int max_rows = (32768 / (2 * MT)) / NB;  // x slab <= 32 KiB of LDS
     max_rows = (max_rows / unit) * unit;
@@ -623,17 +613,25 @@ bool mpq_gemv_fast_ok(int M, int K, int N, int w_bit, int group_size, int dtype,
     return true;
 }
 
+// the v3 kernel's shape rule: whole batches of 8 packed rows, groups of whole batches, an even K.  BIE_GEMV_V3=0: never (A/B arm).
+bool mpq_gemv3_ok(int K, int w_bit, int group_size) {
+    static const int use_v3 = env_int("BIE_GEMV_V3", 1);
+    const int NB = 32 / w_bit;
+    const int rpg = (group_size > K ? K : group_size) / NB;
+    return use_v3 && (K / NB) % 8 == 0 && rpg % 8 == 0 && (K & 1) == 0;
+}
+
+static int gemv_mt(int M) { return M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8)); }
+
+// the workspace of one GEMV launch (v3 or the older form), head included
+size_t mpq_gemv_form_bytes(bool v3, int M, int K, int N, int w_bit, int group_size) {
+    const int S = v3 ? plan_gemv3(K, N, w_bit).S : plan_gemv(K, N, w_bit, group_size, gemv_mt(M)).S;
+    return BIE_WS_HEAD_BYTES + (S > 1 ? (size_t)S * M * N * sizeof(float) : 0);
+}
+
 size_t mpq_gemv_workspace_bytes(int M, int K, int N, int w_bit) {
-    size_t lut = 0;  // the group size is not known here: take the largest slab count any supported group size gives
-    if ((w_bit == 4 && M <= 32) || (w_bit == 2 && M <= 2))  // W4: 17 .. 32 rows may take the matrix-pipe decode kernel with two row blocks (mpq_lut_rb2_ok)
-        for (int gs = 32; gs <= 256; gs *= 2)
-            if (K % gs == 0) {
-                const size_t f = mpq_gemv_lut_part_floats(M, K, gs, cdiv(N, 64), w_bit);
-                if (f > lut) lut = f;
-            }
-    lut = lut ? lut * sizeof(float) + BIE_WS_HEAD_BYTES : 0;
-    const int MT = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
-    const GemvPlan pl = plan_gemv(K, N, w_bit, K, MT);
+    const size_t lut = mpq_gemv_lut_workspace_bytes(M, K, cdiv(N, 64), w_bit);
+    const GemvPlan pl = plan_gemv(K, N, w_bit, K, gemv_mt(M));
     size_t fast = pl.S > 1 ? (size_t)pl.S * M * N * sizeof(float) + BIE_WS_HEAD_BYTES : 0;
     const Gemv3Plan p3 = plan_gemv3(K, N, w_bit);
     const size_t fast3 = p3.S > 1 ? (size_t)p3.S * M * N * sizeof(float) + BIE_WS_HEAD_BYTES : 0;
@@ -643,22 +641,12 @@ size_t mpq_gemv_workspace_bytes(int M, int K, int N, int w_bit) {
     return fast > generic ? fast : generic;
 }
 
-int mpq_gemv_launch(const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
+// v3: the dot2 kernel (mpq_gemv3_ok, no perm); otherwise the older kernel.  part: the workspace, head first.
+int mpq_gemv_launch(bool v3, const void* x, const int32_t* qw, const void* scales, const void* zeros, const void* bias, void* y,
                     float* part, int M, int K, int N, int w_bit, int group_size, int zm, int dtype, const uint16_t* perm,
                     hipStream_t st) {
-    if (perm == nullptr && cdiv(N, 64) <= BIE_WS_COUNTERS && mpq_gemv_lut_ok(M, K, w_bit, group_size, dtype, false, N)) {  // W4: table-lookup / matrix-pipe decode kernels
-        const void* sc1[1] = {scales};
-        const void* ze1[1] = {zeros};
-        const void* bi1[1] = {bias};
-        void* y1[1] = {y};
-        return mpq_gemv_lut_launch(1, &qw, sc1, ze1, bias ? bi1 : nullptr, y1, &N, x, reinterpret_cast<unsigned*>(part) + BIE_WS_GEN_OFFSET,
-                                   part + BIE_WS_HEAD_BYTES / sizeof(float), M, K, group_size, zm, dtype, st, w_bit);
-    }
-    const int MT = M <= 1 ? 1 : (M <= 2 ? 2 : (M <= 4 ? 4 : 8));
-    static const int use_v3 = env_int("BIE_GEMV_V3", 1);
-    const int NBv = 32 / w_bit;
-    const int rpg = (group_size > K ? K : group_size) / NBv;
-    if (perm == nullptr && use_v3 && (K / NBv) % 8 == 0 && rpg % 8 == 0 && (K & 1) == 0) {
+    const int MT = gemv_mt(M);
+    if (v3) {
         const Gemv3Plan p3 = plan_gemv3(K, N, w_bit);
         if (dtype == BIE_F16) return launch_gemv3_w<BIE_F16>(p3, MT, w_bit, zm, x, qw, scales, zeros, bias, part, y, M, K, N, group_size, st);
         return launch_gemv3_w<BIE_BF16>(p3, MT, w_bit, zm, x, qw, scales, zeros, bias, part, y, M, K, N, group_size, st);

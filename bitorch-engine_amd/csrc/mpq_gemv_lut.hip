@@ -26,6 +26,7 @@
 // REPLAY of a captured launch carries the same call number but the next generation)}; nothing ever has to be reset.  `bie_mpq_forward_grouped` passes several weight sets that share x
 // (q/k/v, gate/up): their column tiles are concatenated into one grid.
 #include "mpq_dequant.cuh"
+#include "mpq_plan.h"
 #include "mpq_list.h"
 #include <stdlib.h>
 #include <atomic>
@@ -37,7 +38,6 @@ namespace bie {
 unsigned* device_status_word();                            // splitk.hip
 void test_forge_get(unsigned* tag_skew, int* spin_limit);  // splitk.hip
 // mpq_list.hip: the layer-list kernel with its entries in the kernel arguments (W4, M = 1, bf16: what bie_mpq_forward[_grouped] run on)
-bool mpq_list_inline_ok(int M, int K, long n_total, int w_bit, int group_size, int zm, int dtype);
 size_t mpq_list_inline_part_floats(int M, int K, int group_size, int tiles_total, int w_bit);
 int mpq_list_inline_launch(int nsets, const int32_t* const* qw, const void* const* scales, const void* const* zeros, const void* const* bias,
                            void* const* y, const int* N, const void* x, unsigned* gen, float* gran, int K, int group_size, int zm, hipStream_t st);
@@ -1346,32 +1346,30 @@ extern "C" int bie_debug_lut_stamps(unsigned long long* out, int n_waves) {
 #endif
 
 // ---- host side --------------------------------------------------------------------------------------------
-static int lut_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // W4, implicit groups of 32 / 64 / 128 / 256 that tile K exactly.  FMA form: bf16, M <= 2.  Matrix-pipe form: fp16 / bf16, M <= 16 per layer (17 .. 32 in list launches only).
 // Measured (4096x11008 / 4096x4096, us per launch): bf16 M = 1: FMA form 10.05 / 5.92, matrix-pipe 11.66 / 6.84 -> FMA form;
 // M = 2: 15.1 / 7.3 against 11.8 / 6.8; M = 4, 8, 16: 12.2 / 7.3, 13.0 / 7.9, 15.7 / 10.0 against the MFMA GEMM's 18.7-20.2 /
 // 10.5-12.2 -> matrix-pipe form for 2 <= M <= 16.  fp16 has no FMA form: matrix-pipe from M = 1 (11.5 us against the dot2
 // kernel's 11.9).
 static bool lut_use_mfma(int M, int dtype) {
-    static const int v = lut_env("BIE_LUT_MFMA", 1);
-    static const int lo = lut_env("BIE_LUT_MFMA_MIN_M", 2);
-    static const int hi = lut_env("BIE_LUT_MFMA_MAX_M", 16);
-    static const int lo16 = lut_env("BIE_LUT_MFMA_MIN_M_F16", 2);
+    static const int v = env_int("BIE_LUT_MFMA", 1);
+    static const int lo = env_int("BIE_LUT_MFMA_MIN_M", 2);
+    static const int hi = env_int("BIE_LUT_MFMA_MAX_M", 16);
+    static const int lo16 = env_int("BIE_LUT_MFMA_MIN_M_F16", 2);
     return v != 0 && M >= (dtype == BIE_F16 ? lo16 : lo) && M <= hi && M <= 32;  // hi defaults to 16; 17 .. 32 (two row blocks) is an A/B arm: BIE_LUT_MFMA_MAX_M=32 with BIE_LUT_MAX_M=32
 }
 #include "mpq_lut_rb2_table.inc"
+static bool lut_rb2_on() {
+    static const int on = env_int("BIE_LUT_RB2", 1);
+    return on != 0;
+}
 
 // 17 .. 32 rows of a LONE W4 call on the matrix-pipe decode kernel with two row blocks (RB = 2) instead of the fused MFMA GEMM + its finalize launch: round 6's
 // fp16 arithmetic form made it the faster one on most 4096- and 8192-wide layers (4096x4096 fp16: 10.2 / 11.6 / 14.2 against 12.3 / 13.5 / 15.0 us at 17 / 24 / 32 rows;
 // 4096x8192: 0.75-0.82 of the GEMM's time) and it is 1.2-1.7 x slower on narrow or very wide ones -- so the answer is the measurement, per dtype and exact shape
 // (profiles/r06_lone_rb2_sweep.txt -> mpq_lut_rb2_table.inc); shapes outside the table keep the GEMM.  BIE_LUT_RB2=0: never.
 bool mpq_lut_rb2_ok(int M, int K, int N, int dtype) {
-    static const int on = lut_env("BIE_LUT_RB2", 1);
-    if (!on || M <= 16 || M > 32 || (dtype != BIE_F16 && dtype != BIE_BF16)) return false;
+    if (!lut_rb2_on() || M <= 16 || M > 32 || (dtype != BIE_F16 && dtype != BIE_BF16)) return false;
     for (const auto& e : kLutRb2)
         if (e[0] == K && e[1] == N) return M <= e[dtype == BIE_F16 ? 2 : 3];
     return false;
@@ -1381,15 +1379,14 @@ bool mpq_lut_rb2_ok(int M, int K, int N, int dtype) {
 // lone calls in fp16 (bf16: 21.5 / 24.0 / 27.3 against 34.6 / 38.7 / 45.3), an 8192 -> 8192 + 1024 + 1024 set 0.55-0.73 of the lone calls' time; gate/up (2 x 4096x11008): fp16
 // 0.79-0.80, bf16 1.01-1.15 -- so fp16 always, bf16 (table form) up to 16384 output columns in the set (profiles/r06_grouped_rb2_probe.txt).
 bool mpq_lut_rb2_grouped_ok(int M, int K, long n_total, int dtype) {
-    static const int on = lut_env("BIE_LUT_RB2", 1);
     (void)K;
-    if (!on || M <= 16 || M > 32) return false;
+    if (!lut_rb2_on() || M <= 16 || M > 32) return false;
     return dtype == BIE_F16 || (dtype == BIE_BF16 && n_total <= 16384);
 }
 
 bool mpq_gemv_lut_ok(int M, int K, int w_bit, int group_size, int dtype, bool has_gidx, int N) {
-    static const int enabled = lut_env("BIE_GEMV_LUT", 1);
-    static const int w2 = lut_env("BIE_GEMV_LUT_W2", 1);
+    static const int enabled = env_int("BIE_GEMV_LUT", 1);
+    static const int w2 = env_int("BIE_GEMV_LUT_W2", 1);
     if (!enabled || has_gidx || M < 1) return false;
     if (dtype != BIE_BF16 && dtype != BIE_F16) return false;
     const int gs = group_size > K ? K : group_size;
@@ -1414,12 +1411,12 @@ struct LutPlan {
 // per-wave critical path, which is what a 4096x4096 launch spends its time on, shrinks accordingly); big grids give a wave
 // several units (bounds the granule traffic).
 static LutPlan lut_plan(int M, int dtype, int K, int group_size, int tiles_total, int w_bit = 4) {
-    static const int min_rows = lut_env("BIE_LUT_ROWS", 16);
-    static const int nw_env = lut_env("BIE_LUT_NW", 8);
-    static const int max_wg = lut_env("BIE_LUT_MAX_WG", 2048);
-    static const int coop = lut_env("BIE_LUT_COOP", 0);  // measured slower (12.1 vs 10.1 us at 4096x11008): kept as a tuning variant
-    static const int force_h = lut_env("BIE_LUT_H", 0);
-    static const int want_waves = lut_env("BIE_LUT_WANT_WAVES", 4096);
+    static const int min_rows = env_int("BIE_LUT_ROWS", 16);
+    static const int nw_env = env_int("BIE_LUT_NW", 8);
+    static const int max_wg = env_int("BIE_LUT_MAX_WG", 2048);
+    static const int coop = env_int("BIE_LUT_COOP", 0);  // measured slower (12.1 vs 10.1 us at 4096x11008): kept as a tuning variant
+    static const int force_h = env_int("BIE_LUT_H", 0);
+    static const int want_waves = env_int("BIE_LUT_WANT_WAVES", 4096);
     LutPlan p;
     const int gs = group_size > K ? K : group_size;
     p.rpg = gs / (32 / w_bit);
@@ -1453,15 +1450,29 @@ static LutPlan lut_plan(int M, int dtype, int K, int group_size, int tiles_total
 }
 
 // granule area behind the workspace head, counted in floats (a granule = 8 bytes)
-size_t mpq_gemv_lut_part_floats(int M, int K, int group_size, int tiles_total, int w_bit) {
-    size_t need = 0;  // the dtype is not known where workspaces are sized: the larger of the two plans
-    for (int dtype : {BIE_F16, BIE_BF16}) {
-        const LutPlan p = lut_plan(M, dtype, K, group_size, tiles_total, w_bit);
-        const size_t f = p.S > 1 ? (size_t)(p.S - 1) * M * tiles_total * 64 * 2 : 0;
-        if (f > need) need = f;
-    }
-    const size_t inl = mpq_list_inline_part_floats(M, K, group_size, tiles_total, w_bit);
-    return inl > need ? inl : need;
+static size_t lut_part_floats(int M, int K, int group_size, int tiles_total, int w_bit, int dtype) {
+    const LutPlan p = lut_plan(M, dtype, K, group_size, tiles_total, w_bit);
+    return p.S > 1 ? (size_t)(p.S - 1) * M * tiles_total * 64 * 2 : 0;
+}
+
+// the workspace of one decode launch (the lookup kernels, or the inline list form), head included
+size_t mpq_gemv_lut_bytes(bool inline_list, int M, int K, int group_size, int tiles_total, int w_bit, int dtype) {
+    const size_t f = inline_list ? mpq_list_inline_part_floats(M, K, group_size, tiles_total, w_bit) : lut_part_floats(M, K, group_size, tiles_total, w_bit, dtype);
+    return BIE_WS_HEAD_BYTES + f * sizeof(float);
+}
+
+// ... for sizing, where the dtype and the group size are not known: the largest any of them gives, or 0 where no decode form takes
+// the rows (W4: up to 32, 17 .. 32 with two row blocks; W2: up to 2)
+size_t mpq_gemv_lut_workspace_bytes(int M, int K, int tiles_total, int w_bit) {
+    if (!((w_bit == 4 && M <= 32) || (w_bit == 2 && M <= 2))) return 0;
+    size_t f = 0;
+    for (int gs = 32; gs <= 256; gs *= 2)
+        if (K % gs == 0) {
+            for (int dtype : {BIE_F16, BIE_BF16})
+                if (lut_part_floats(M, K, gs, tiles_total, w_bit, dtype) > f) f = lut_part_floats(M, K, gs, tiles_total, w_bit, dtype);
+            if (mpq_list_inline_part_floats(M, K, gs, tiles_total, w_bit) > f) f = mpq_list_inline_part_floats(M, K, gs, tiles_total, w_bit);
+        }
+    return f ? BIE_WS_HEAD_BYTES + f * sizeof(float) : 0;
 }
 
 // fp16 W4 FMA form
@@ -1510,8 +1521,8 @@ static void lut2_launch(const LutArgs& a, int rpg, int grid, int M, int zm, hipS
 
 template <int DT, int ZM, int MT, int NW>
 static void lut_launch_rpg(const LutArgs& a, int rpg, int grid, hipStream_t st) {
-    static const int lab = lut_env("BIE_GEMV_LAB", 0);
-    static const int rd = lut_env("BIE_LUT_RD", 0);
+    static const int lab = env_int("BIE_GEMV_LAB", 0);
+    static const int rd = env_int("BIE_LUT_RD", 0);
 #define BIE_LUT(RPGV)                                                                                                       \
     do {                                                                                                                    \
         if (lab == 0 && rd > 0 && RPGV == 16 && MT == 1 && ZM == ZM_SYM) {                                                  \
@@ -1553,7 +1564,7 @@ static void lut_launch_nw(const LutArgs& a, int rpg, int grid, int M, int zm, hi
 
 template <int ZM, int MT>
 static void lutc_launch_rpg(const LutArgs& a, int rpg, int grid, hipStream_t st) {
-    static const int lab = lut_env("BIE_GEMV_LAB", 0);
+    static const int lab = env_int("BIE_GEMV_LAB", 0);
 #define BIE_LUTC(RPGV, LABV) hipLaunchKernelGGL((mpq_gemv_lutc_kernel<BIE_BF16, ZM, MT, RPGV, LABV>), dim3(grid), dim3(256), 0, st, a)
     if (lab != 0 && rpg == 16 && MT == 1 && ZM == ZM_SYM) {
         if (lab == 2) hipLaunchKernelGGL((mpq_gemv_lutc_kernel<BIE_BF16, ZM_SYM, 1, 16, 2>), dim3(grid), dim3(256), 0, st, a);
@@ -1625,8 +1636,8 @@ static void lutm_list_launch_dt(const ListEntry* ent, const uint2_t* blk, unsign
 // 10.3 -> 7.7 us per 4096x11008 layer at 32 rows.  M <= 16: same residency either way, but a wave walks twice the units (prologue, barriers and
 // the workgroup reduction amortised): 6.48 -> 5.96 us at 16 rows (profiles/r05_lutm_list_nw_ab.txt).  BIE_LUTM_NW32 / BIE_LUTM_NW16 = 8: the old plan.
 int mpq_lutm_list_nw(int M) {
-    static const int nw32 = lut_env("BIE_LUTM_NW32", 4);
-    static const int nw16 = lut_env("BIE_LUTM_NW16", 4);
+    static const int nw32 = env_int("BIE_LUTM_NW32", 4);
+    static const int nw16 = env_int("BIE_LUTM_NW16", 4);
     return M > 16 ? (nw32 == 8 ? 8 : 4) : (nw16 == 8 ? 8 : 4);
 }
 int mpq_lutm_list_launch(const ListEntry* ent, const uint2_t* blk, unsigned grid, int M, int rpg, int zm, int dtype, int nw, hipStream_t st) {
@@ -1686,12 +1697,11 @@ int mpq_lutm_xs_list_launch(const ListEntry* ent, const uint2_t* blk, unsigned g
 }
 
 // sets: n weight sets sharing x (one for a plain forward).  `gen` = the workspace's head, `gran` = granule area.
-int mpq_gemv_lut_launch(int nsets, const int32_t* const* qw, const void* const* scales, const void* const* zeros,
+// form: MpqForm::InlineList (big W4 / M = 1 / bf16 launches: the list kernel's D16 form, entries in the kernel arguments) or MpqForm::Lut.
+int mpq_gemv_lut_launch(MpqForm form, int nsets, const int32_t* const* qw, const void* const* scales, const void* const* zeros,
                         const void* const* bias, void* const* y, const int* N, const void* x, unsigned* gen, float* gran,
                         int M, int K, int group_size, int zm, int dtype, hipStream_t st, int w_bit) {
-    long n_total = 0;
-    for (int i = 0; i < nsets; i++) n_total += N[i];
-    if (mpq_list_inline_ok(M, K, n_total, w_bit, group_size, zm, dtype))  // big W4 / M = 1 / bf16 launches: the list kernel's D16 form, entries in the kernel arguments
+    if (form == MpqForm::InlineList)
         return mpq_list_inline_launch(nsets, qw, scales, zeros, bias, y, N, x, gen, gran, K, group_size, zm, st);
     LutArgs a;
     int tiles = 0;

@@ -756,11 +756,6 @@ extern "C" int bie_debug_list_stamps(unsigned long long* out, int n_waves) {
 // ---- host side ---------------------------------------------------------------------------------------------------
 int status_report(const char* fn);  // splitk.hip
 
-static int list_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 struct ListPlanEntry { int rpg, G, gpw, S, H, tiles, tpb; };  // tpb: column tiles per workgroup (4: the x-sharing matrix-pipe form)
 
 struct MpqList {
@@ -786,17 +781,17 @@ struct MpqList {
 // with eight, 2.2 / 2.1 with two / one: profiles/r03_p_list_nw.txt).  Everything else: eight.  BIE_LIST_NW (tuning aid, lab
 // configuration only) overrides.
 static int list_nw(int M, int w_bit) {
-    static const int nw = list_env("BIE_LIST_NW", 0);
+    static const int nw = env_int("BIE_LIST_NW", 0);
     if (nw == 8 || nw == 4 || nw == 2 || nw == 1) return nw;
     return (M == 1 && w_bit == 4) ? 4 : 8;
 }
 
 static void list_plan(int n, const bie_mpq_list_entry* ent, int w_bit, int group_size, int* rpg_out, std::vector<ListPlanEntry>& pe, int nw = 8, int max_gpw_plan = 0,
                       int want_plan = 0) {
-    static const int want_env = list_env("BIE_LIST_WANT_WAVES", 6144);
+    static const int want_env = env_int("BIE_LIST_WANT_WAVES", 6144);
     const int want = want_plan > 0 ? want_plan : want_env;
-    static const int force_h = list_env("BIE_LIST_H", 0);
-    static const int max_gpw_env = list_env("BIE_LIST_MAX_GPW", 0);
+    static const int force_h = env_int("BIE_LIST_H", 0);
+    static const int max_gpw_env = env_int("BIE_LIST_MAX_GPW", 0);
     const int max_gpw = max_gpw_env > 0 ? max_gpw_env : (max_gpw_plan > 0 ? max_gpw_plan : 16);
     const int NB = 32 / w_bit;
     long units = 0;  // at H = 1
@@ -838,8 +833,7 @@ static void list_plan(int n, const bie_mpq_list_entry* ent, int w_bit, int group
 
 // BIE_LIST_ALG (the opt-in algebraic fp16 form, mpq_list_forward): read once per process; under BIE_TUNING per call (bench.py times both forms in one process)
 static int list_alg_choice() {
-    static const int alg_once = list_env("BIE_LIST_ALG", 0);
-    return getenv("BIE_TUNING") ? list_env("BIE_LIST_ALG", 0) : alg_once;
+    return BIE_KNOB("BIE_LIST_ALG", 0);
 }
 
 // The x-sharing matrix-pipe form (lutm_xs_body, mpq_gemv_lut.hip): a workgroup = four adjacent column tiles over the same `gpw` units, so K is
@@ -849,11 +843,11 @@ static bool list_xs_plan(int n, const bie_mpq_list_entry* ent, int M, int w_bit,
     // plan knobs: read once per process -- per call under BIE_TUNING (tests force the form onto small lists, sweep tools change them between plans)
     struct Knobs { int min_m_f16, min_m_bf16, max_s, max_gpw, want, bf16_whole_pct, nw; };
     auto read_knobs = [] {
-        return Knobs{list_env("BIE_LUTM_XS_MIN_M", 1), list_env("BIE_LUTM_XS_MIN_M_BF16", 12), list_env("BIE_LUTM_XS_MAX_S", 4),
-                     list_env("BIE_LUTM_XS_MAX_GPW", 48), list_env("BIE_LUTM_XS_WANT_WAVES", 5120), list_env("BIE_LUTM_XS_BF16_WHOLE_PCT", 50), list_env("BIE_LUTM_XS_NW", 4)};
+        return Knobs{env_int("BIE_LUTM_XS_MIN_M", 1), env_int("BIE_LUTM_XS_MIN_M_BF16", 12), env_int("BIE_LUTM_XS_MAX_S", 4),
+                     env_int("BIE_LUTM_XS_MAX_GPW", 48), env_int("BIE_LUTM_XS_WANT_WAVES", 5120), env_int("BIE_LUTM_XS_BF16_WHOLE_PCT", 50), env_int("BIE_LUTM_XS_NW", 4)};
     };
     static const Knobs once = read_knobs();
-    const Knobs kn = getenv("BIE_TUNING") ? read_knobs() : once;
+    const Knobs kn = tuning() ? read_knobs() : once;
     const int min_m_f16 = kn.min_m_f16, min_m_bf16 = kn.min_m_bf16, max_s = kn.max_s, max_gpw = kn.max_gpw, want = kn.want;
     const int min_m = dtype == BIE_F16 ? min_m_f16 : (min_m_f16 <= 0 ? 0 : min_m_bf16);
     // waves wanted: 5120 makes two slices of a K = 11008 layer (43 units each) where the k-split plans' 6144 makes three; measured over 40 layers
@@ -972,12 +966,12 @@ int mpq_list_create(MpqList** out, int n, const bie_mpq_list_entry* ent, int M, 
     list_plan(n, ent, w_bit, group_size, &rpg, pe);
     int nw = (M == 1 && w_bit == 4) ? 4 : 8;
     // W2 at one row: four waves as well (+1-2 % on three shapes in both dtypes, profiles/r06_w2_nw_ab.txt); BIE_LIST_W2_NW=8: the eight-wave arm
-    static const int w2_nw = list_env("BIE_LIST_W2_NW", 4);
+    static const int w2_nw = env_int("BIE_LIST_W2_NW", 4);
     if (M == 1 && w_bit == 2 && w2_nw == 4) nw = 4;
     if (dtype == BIE_BF16 && !asym && M == 1 && rpg == 16 && w_bit == 4) nw = list_nw(M, w_bit);  // the lab configuration takes the override
     // Two rows of W4 also go to the matrix-pipe kernel when the entries allow it (independent, N % 4 == 0, 16-byte aligned x): measured
     // 6.6 against 7.5 us per 4096x11008 layer for the two-row FMA form (profiles/r03_z_lutm_list_ab.txt).  BIE_LIST_M2_MFMA=0: FMA form.
-    static const int m2_mfma = list_env("BIE_LIST_M2_MFMA", 1);
+    static const int m2_mfma = env_int("BIE_LIST_M2_MFMA", 1);
     bool lutm = M > 2;
     bool mfma_ok = w_bit == 4;  // what the matrix-pipe kernels ask of the entries (validated above for M > 2)
     for (int i = 0; i < n; i++)
@@ -1114,7 +1108,7 @@ int mpq_list_forward(MpqList* p, hipStream_t st) {
     test_forge_get(&a.tag_skew, &a.spin_limit);
     a.M = p->M;
     a.dep_extra = test_forge_dep_get();
-    static const int var = list_env("BIE_LIST_VAR", 1);  // tuning aid: 0 = scalar FMAs, 1 = v_pk_fma_f32 pairs, 2 / 3 = stream only
+    static const int var = env_int("BIE_LIST_VAR", 1);  // tuning aid: 0 = scalar FMAs, 1 = v_pk_fma_f32 pairs, 2 / 3 = stream only
     const bool lab_ok = p->dtype == BIE_BF16 && p->zm == ZM_SYM && p->M == 1 && p->rpg == 16 && p->w_bit == 4;
     if (lab_ok && p->nw != 4) {
         if (p->nw == 8) hipLaunchKernelGGL((mpq_list_kernel<BIE_BF16, ZM_SYM, 1, 16, 4, 1>), dim3(p->grid), dim3(512), 0, st, a);
@@ -1127,7 +1121,7 @@ int mpq_list_forward(MpqList* p, hipStream_t st) {
         else hipLaunchKernelGGL((mpq_list_kernel<BIE_BF16, ZM_SYM, 1, 16, 4, 11>), dim3(p->grid), dim3(256), 0, st, a);
         return check_launch("mpq_list_kernel<lab>");
     }
-    static const int d16 = list_env("BIE_LIST_D16", 1);  // the 16-bit-table form of the W4 / M = 1 kernel (0: the fp32-table form)
+    static const int d16 = env_int("BIE_LIST_D16", 1);  // the 16-bit-table form of the W4 / M = 1 kernel (0: the fp32-table form)
     // fp16, independent entries: BIE_LIST_ALG=1 selects the ALGEBRAIC form (template bit 12) -- 0.79-0.82 of HBM on the bench's W4 lists against
     // 0.64-0.7 for the table forms, but its results are the EXACT products' sums, 6-8e-4 of max|y| away from the reference's doubly rounded
     // weights (profiles/r05_list_alg_ab_a.txt, gpurun_out/rel_err_report.txt): inside north_star's 1e-3 norm-wise, not element by element, so
@@ -1144,13 +1138,13 @@ int mpq_list_forward(MpqList* p, hipStream_t st) {
     }
     if (d16 && p->w_bit == 4 && p->dtype == BIE_BF16 && p->M == 1 && p->nw == 4) {
 #ifdef BIE_LAB_BUILD
-        static const int ring2 = list_env("BIE_LIST_RING2", 0);  // lab builds: two lookup chunks in flight, 1 = default registers, 7 = 7 waves per SIMD forced
+        static const int ring2 = env_int("BIE_LIST_RING2", 0);  // lab builds: two lookup chunks in flight, 1 = default registers, 7 = 7 waves per SIMD forced
         if (ring2 && p->rpg == 16 && p->zm == ZM_SYM) {
             if (ring2 == 7) hipLaunchKernelGGL((mpq_list_kernel<BIE_BF16, ZM_SYM, 1, 16, 4, 1 | 8 | 64 | 2048 | 128>), dim3(p->grid), dim3(256), 0, st, a);
             else hipLaunchKernelGGL((mpq_list_kernel<BIE_BF16, ZM_SYM, 1, 16, 4, 1 | 8 | 64 | 2048>), dim3(p->grid), dim3(256), 0, st, a);
             return check_launch("mpq_list_kernel<d16,ring2>");
         }
-        static const int abl = list_env("BIE_LIST_ABL", 0);  // lab builds: 1 no LDS reads, 2 no FMAs, 4 no table build (sums allowed: 3, 5, 6, 7)
+        static const int abl = env_int("BIE_LIST_ABL", 0);  // lab builds: 1 no LDS reads, 2 no FMAs, 4 no table build (sums allowed: 3, 5, 6, 7)
         if (abl && p->rpg == 16 && p->zm == ZM_SYM) {
 #define BIE_ABL(A) case A: hipLaunchKernelGGL((mpq_list_kernel<BIE_BF16, ZM_SYM, 1, 16, 4, 1 | 8 | 64 | (A << 8)>), dim3(p->grid), dim3(256), 0, st, a); break;
             switch (abl) { BIE_ABL(1) BIE_ABL(2) BIE_ABL(3) BIE_ABL(4) BIE_ABL(5) BIE_ABL(6) BIE_ABL(7) default: break; }
@@ -1182,11 +1176,11 @@ int mpq_list_forward(MpqList* p, hipStream_t st) {
 struct InlinePlan { int rpg, G, H, gpw, S, nw; };
 
 static InlinePlan inline_plan(int K, int group_size, int tiles_total) {
-    static const int want = list_env("BIE_INL_WANT_WAVES", 4096);
-    static const int max_waves = list_env("BIE_INL_MAX_WAVES", 16384);  // more waves than are resident at once: the second round starts staggered (117 MB: 29.3 against 31.0 us at 6144, 250 MB: 52.4 against 56.3; profiles/r04_t_inl_big_sweep.txt)
-    static const int force_h = list_env("BIE_INL_H", 0);
-    static const int force_gpw = list_env("BIE_INL_GPW", 0);
-    static const int nw_env = list_env("BIE_INL_NW", 4);
+    static const int want = env_int("BIE_INL_WANT_WAVES", 4096);
+    static const int max_waves = env_int("BIE_INL_MAX_WAVES", 16384);  // more waves than are resident at once: the second round starts staggered (117 MB: 29.3 against 31.0 us at 6144, 250 MB: 52.4 against 56.3; profiles/r04_t_inl_big_sweep.txt)
+    static const int force_h = env_int("BIE_INL_H", 0);
+    static const int force_gpw = env_int("BIE_INL_GPW", 0);
+    static const int nw_env = env_int("BIE_INL_NW", 4);
     InlinePlan p;
     p.nw = nw_env == 4 ? 4 : 8;
     const int gs = group_size > K ? K : group_size;
@@ -1212,8 +1206,8 @@ static InlinePlan inline_plan(int K, int group_size, int tiles_total) {
 // by its ramp, its per-wave latency chain and the cross-workgroup reduction, not by instruction count, and the older kernel's 8 waves per
 // SIMD hide that chain better; the list form's leaner stream only pays from ~96 MB of packed weights per launch.
 bool mpq_list_inline_ok(int M, int K, long n_total, int w_bit, int group_size, int zm, int dtype) {
-    static const int enabled = list_env("BIE_DECODE_INLINE", 1);  // 0: never; 2: always (tuning)
-    static const long min_mb = list_env("BIE_DECODE_INLINE_MIN_MB", 40);  // round 6: 96 -> 40 (gate/up of a 7B layer, 45 MB: 16.1 -> 15.5 us; profiles/r06_lone_plan_sweeps.txt)
+    static const int enabled = env_int("BIE_DECODE_INLINE", 1);  // 0: never; 2: always (tuning)
+    static const long min_mb = env_int("BIE_DECODE_INLINE_MIN_MB", 40);  // round 6: 96 -> 40 (gate/up of a 7B layer, 45 MB: 16.1 -> 15.5 us; profiles/r06_lone_plan_sweeps.txt)
     if (!enabled || M != 1 || w_bit != 4 || dtype != BIE_BF16 || (zm != ZM_SYM && zm != ZM_ASYM)) return false;
     const int gs = group_size > K ? K : group_size;
     if (!((gs == 32 || gs == 64 || gs == 128 || gs == 256) && K % gs == 0)) return false;

@@ -3,6 +3,7 @@
  * hand-offs fail loudly. */
 #ifndef BIE_HIP_TESTING_H
 #define BIE_HIP_TESTING_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -14,6 +15,10 @@ void bie_test_forge_reducer(unsigned tag_skew, int spin_limit);
 /* Make dependent list entries of subsequent launches wait for `extra` more producer tiles than exist (a producer that never
  * finishes); 0 restores normal operation. */
 void bie_test_forge_dependency(int extra);
+/* Which kernel bie_mpq_forward would launch for a call of this shape (sym, no perm; workspace_bytes as the caller passes it), and the
+ * workspace that kernel uses in *need (when need is not NULL).  Host only.  Returns the form: 0 the decode (lookup) kernels, 1 the inline
+ * list kernel, 2 the v3 GEMV, 3 the older GEMV, 4 the fused MFMA GEMM, 5 dequantise + dense GEMM, 6 the g_idx dense form, 7 generic. */
+int bie_test_mpq_forward_plan(int M, int K, int N, int w_bit, int group_size, int dtype, int has_gidx, size_t workspace_bytes, size_t* need);
 
 #ifdef __cplusplus
 }

@@ -259,6 +259,77 @@ def test_workspace_sizing_is_total_over_row_counts_and_shapes():
                 assert L.bie_mpq_workspace_bytes(M, K, N, w_bit) > 0, (M, K, N, w_bit)
 
 
+MPQ_FORMS = {"lut": 0, "inline_list": 1, "gemv3": 2, "gemv": 3, "gemm_fused": 4, "gemm_dense": 5, "gidx_dense": 6, "generic": 7}
+
+
+def _mpq_plan(L, M, K, N, w, gs, dt, gidx=0, ws=0):
+    need = ctypes.c_size_t(0)
+    form = L.bie_test_mpq_forward_plan(M, K, N, w, gs, dt, gidx, ws, ctypes.byref(need))
+    return form, need.value
+
+
+def test_forward_plan_reaches_every_form():
+    """bie_test_mpq_forward_plan (host-only, include/bie_hip_testing.h): the kernel bie_mpq_forward launches, at default knobs, for a table of calls
+    that reaches every form of csrc/mpq_plan.h."""
+    from bitorch_engine import _hip
+    L = _hip.lib()
+    F16, BF16, F32 = _hip.F16, _hip.BF16, _hip.F32
+    dense_ws = 16384 + 4096 * 4096 * 2  # head + the K x N fragment image (bie_mpq_workspace_bytes_gidx)
+    cases = (
+        (1, 4096, 4096, 4, 128, F16, 0, 0, "lut"),            # fp16 decode: the lookup kernel from one row
+        (1, 4096, 4096, 4, 128, BF16, 0, 0, "lut"),           # bf16, below the inline form's 40 MB
+        (16, 4096, 4096, 4, 128, BF16, 0, 0, "lut"),
+        (17, 4096, 4096, 4, 128, F16, 0, 0, "lut"),           # on the RB=2 table
+        (32, 4096, 8192, 4, 128, F16, 0, 0, "lut"),
+        (24, 4096, 11008, 4, 128, BF16, 0, 0, "gemm_fused"),  # on the table, beyond its bf16 row count
+        (24, 4096, 2048, 4, 128, F16, 0, 0, "gemm_fused"),    # off the table
+        (17, 4096, 4160, 4, 128, F16, 0, 0, "gemm_fused"),
+        (2, 4096, 4096, 2, 128, F16, 0, 0, "lut"),            # W2: two rows at most
+        (3, 4096, 4096, 2, 128, F16, 0, 0, "gemm_fused"),
+        (1, 4096, 28672, 4, 128, BF16, 0, 0, "inline_list"),  # W4 / M = 1 / bf16 from 40 MB of weights
+        (1, 4096, 4096, 8, 128, F16, 0, 0, "gemv3"),
+        (2, 4096, 4096, 1, 256, BF16, 0, 0, "gemv3"),
+        (2, 4096, 4096, 1, 128, BF16, 0, 0, "gemv"),          # W1 groups of 128: 4 packed rows
+        (1, 4096, 4096, 8, 16, F16, 0, 0, "gemv"),            # groups of 4 packed rows: not whole batches of 8
+        (64, 4096, 4096, 4, 128, F16, 0, 0, "gemm_fused"),
+        (1024, 4096, 4096, 4, 128, BF16, 0, 0, "gemm_dense"),
+        (64, 4096, 4096, 4, 128, BF16, 1, dense_ws, "gidx_dense"),
+        (64, 4096, 4096, 4, 128, BF16, 1, dense_ws - 1, "generic"),  # the caller did not size the workspace for the image
+        (1, 4096, 4096, 4, 128, F16, 1, 0, "generic"),
+        (4, 4096, 4096, 4, 128, F32, 0, 0, "generic"),
+        (1, 4096, 4098, 4, 128, F16, 0, 0, "generic"),        # odd N
+    )
+    seen = set()
+    for (M, K, N, w, gs, dt, gidx, ws, want) in cases:
+        form, need = _mpq_plan(L, M, K, N, w, gs, dt, gidx, ws)
+        assert form == MPQ_FORMS[want], (M, K, N, w, gs, dt, gidx, ws, form, want)
+        assert need >= 16384
+        seen.add(form)
+    assert seen == set(MPQ_FORMS.values())
+    # the rows form agrees with the plan where the decode kernels are tried first
+    for (M, K, N, w, dt) in ((1, 4096, 4096, 4, BF16), (17, 4096, 4096, 4, F16), (24, 4096, 11008, 4, BF16), (3, 4096, 4096, 2, F16)):
+        assert (L.bie_mpq_rows_form(M, K, N, w, 128, dt) == 2) == (_mpq_plan(L, M, K, N, w, 128, dt)[0] in (0, 1)), (M, K, N, w, dt)
+
+
+def test_workspace_sizing_covers_every_plan():
+    """bie_mpq_workspace_bytes (and the grouped sizing, which the per-set fallback of bie_mpq_forward_grouped runs in) is at least the workspace
+    of the kernel every call of those sizes launches, whatever its group size and dtype."""
+    from bitorch_engine import _hip
+    L = _hip.lib()
+    shapes = ((4096, 4096), (4096, 11008), (11008, 4096), (4096, 2048), (4096, 6144), (4096, 8192), (4096, 28672), (4096, 100), (11008, 4100), (1024, 12))
+    rows = list(range(1, 34)) + [64, 897, 1024, 4096]
+    for (K, N) in shapes:
+        for w in (1, 2, 4, 8):
+            for M in rows:
+                total = L.bie_mpq_workspace_bytes(M, K, N, w)
+                grouped = L.bie_mpq_grouped_workspace_bytes(3, (ctypes.c_int * 3)(N, N, 1024), M, K, w)
+                for gs in (32, 64, 128, 256):
+                    for dt in (_hip.F16, _hip.BF16):
+                        form, need = _mpq_plan(L, M, K, N, w, gs, dt)
+                        assert need <= total, (M, K, N, w, gs, dt, form, need, total)
+                        assert need <= grouped, (M, K, N, w, gs, dt, form, need, grouped)
+
+
 def test_prefill_dispatch_follows_the_measured_table_inside_its_grid(monkeypatch):
     """mpq_dense_ok (csrc/mpq_dense.hip): inside the measured grid the dense two-launch form is chosen where the sweep found it faster
     (profiles/r06_dense_rule_sweep.txt -> csrc/mpq_dense_table.inc), by the nearest grid point in log space; outside the grid and with
