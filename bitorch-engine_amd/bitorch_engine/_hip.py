@@ -101,6 +101,12 @@ SIGNATURES = {
     "bie_int_gemm_i32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _l, _l, _vp]),
     "bie_q4_conv2d_workspace_bytes": (_sz, [_i] * 9),
     "bie_q4_conv2d_forward": (_i, [_vp, _vp, _vp, _vp, _sz] + [_i] * 9 + [_f, _f, _i, _vp]),
+    "bie_ternary_pack": (_i, [_vp, _vp, _l, _l, _vp]),
+    "bie_ternary_unpack": (_i, [_vp, _vp, _l, _l, _vp]),
+    "bie_ternary_fp4_image": (_i, [_vp, _vp, _l, _l, _vp]),
+    "bie_ternary_linear_fused_ok": (_i, [_l] * 3),
+    "bie_ternary_linear_fused": (_i, [_vp] * 6 + [_l] * 3 + [_i, _i, _vp]),
+    "bie_ternary_linear_layer_fp4": (_i, [_vp] * 5 + [_l] * 3 + [_i, _vp]),
 }
 
 

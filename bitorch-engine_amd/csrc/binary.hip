@@ -17,18 +17,6 @@ __device__ __forceinline__ bool sign_bit(const void* p, long i) {
     else return dt_traits<DT>::load(p, i) >= 0.0f;
 }
 
-// Wave-wide integer sum on the DPP network (no LDS traffic): quad swaps, half-row and row mirrors, then the two row broadcasts;
-// the total lands in lane 63 and is read back as a scalar.
-__device__ __forceinline__ int wave_sum_dpp(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror: every lane of a row holds the row's sum
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // ---- packing ---------------------------------------------------------------------------------------------
 // rows x K values -> rows x K/8 bytes, LSB first.  One thread per output byte.
 template <int DT>

@@ -189,7 +189,8 @@ __device__ __forceinline__ void mfma_fp4(float16_t& c, const v4i_t& a, const v4i
 // output channels: y fp32 [B, N, conv_p] (NCHW), y[(b * N + n) * conv_p + p].  ODT = BIE_F16 / BF16 / F32: the BinaryLinearCuda layer epilogue, y (ODT) =
 // dt(dt(dt(K - 2*popc) * scale_a) * scale_w) with scale_a / scale_w device scalars of that dtype (NULL = 1): the roundings of
 // `forward(...).to(input.dtype) * scale_a * scale_w` (layers/qlinear/binary/cuda/layer.py:58-63), as xnor_fused_kernel.
-template <int WM, int WN, int VAR, int ODT>
+// CS (layer epilogues only): scale_w is a vector over the output columns, sw[n] (the ternary layer's alpha, ternary.hip).
+template <int WM, int WN, int VAR, int ODT, bool CS = false>
 __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, void* __restrict__ yv, int M, int N,
                                                             int KT, int RBA, int RBB, int tiles_n, float scale, const void* __restrict__ scale_a,
                                                             const void* __restrict__ scale_w, int conv_p) {
@@ -341,6 +342,19 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
     // four registers, FOUR CONSECUTIVE n: one 16-byte store per group (64 per lane instead of 256 dword stores -- the dword form was
     // store-issue bound: 13 us of fixed cost per launch, profiles/r03_fp4_c_k_slope.txt).
     const int m_l = lane & 31;
+    // CS: the tile's BF * 32 column scales are staged once in LDS (one global load per thread, one barrier); the epilogue reads them from
+    // there.  Loaded from global memory per value inside the row loop, every load was waited on at once (and a vmcnt wait also drains the
+    // y stores in flight): 1.16 - 1.39 x the binary epilogue's kernel time at M = 4096, against 0.98 - 1.06 x staged
+    // (profiles/ternary_gemm_epilogue.txt).
+    __shared__ __attribute__((aligned(16))) float csw[CS ? BF * 32 : 1];
+    if constexpr (CS && ODT >= 0) {
+        if (threadIdx.x < BF * 32) {
+            const int n = min(tile_n * BF * 32 + (int)threadIdx.x, N - 1);  // padding columns: never stored
+            csw[threadIdx.x] = scale_w ? dt_traits<ODT>::load(scale_w, n) : 1.0f;
+        }
+        __syncthreads();
+    }
+    const int n_tile0 = tile_n * BF * 32;  // column of csw[0]
     if constexpr (ODT == -2) {
         // NCHW scatter: for one register the 32 lanes of a half-wave hold 32 consecutive pixels of one channel -> dword stores, contiguous
         // across lanes inside an image
@@ -368,7 +382,7 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
         float sa = 1.0f, sw = 1.0f;
         if constexpr (ODT == BIE_F32) {
             if (scale_a) sa = *(const float*)scale_a;
-            if (scale_w) sw = *(const float*)scale_w;
+            if (scale_w && !CS) sw = *(const float*)scale_w;
         }
         const int n_l = 4 * (lane >> 5);
         const bool vec_ok = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
@@ -387,6 +401,7 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
 #pragma unroll
                         for (int e = 0; e < 4; e++) {
                             if constexpr (ODT < 0) v[e] = acc[i][j][4 * q + e] * scale;
+                            else if constexpr (CS) v[e] = (acc[i][j][4 * q + e] * sa) * csw[n - n_tile0 + e];
                             else v[e] = (acc[i][j][4 * q + e] * sa) * sw;  // fp32 layer: two rounded multiplies
                         }
                         if (vec_ok && n + 3 < N) *reinterpret_cast<float4_t*>(yr + n) = v;
@@ -404,21 +419,21 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
         // quads of register groups q and q + 1 between them, after which a lane owns 8 consecutive n of group 2*(q/2) + (lane >> 5):
         // one 16-byte store (32 per lane)
         uint16_t* y = (uint16_t*)yv;
-        const float sa = scale_a ? dt_traits<ODT>::load(scale_a, 0) : 1.0f, sw = scale_w ? dt_traits<ODT>::load(scale_w, 0) : 1.0f;
+        const float sa = scale_a ? dt_traits<ODT>::load(scale_a, 0) : 1.0f, sw = scale_w && !CS ? dt_traits<ODT>::load(scale_w, 0) : 1.0f;
         // The three roundings on PAIRS (the generic per-value form -- round, multiply, round, multiply, round, pack -- was 11 VALU per value,
         // 2900 per wave): bf16: v_cvt_pk_bf16_f32 is rounding and pack in one; the two halves are widened (shift / mask), multiplied in
         // fp32 (exact products of two bf16 values) and re-packed: 5.5 per value.  fp16: v_pk_mul_f16 IS dt(v * s) for fp16 operands
         // (the fp32 product of two fp16 values is exact, so one rounding either way): 2.5 per value.
-        auto fin2 = [&](float c0, float c1) -> uint32_t {
+        auto fin2 = [&](float c0, float c1, float sw0, float sw1) -> uint32_t {
             if constexpr (ODT == BIE_BF16) {
                 uint32_t p = pack_bf16x2(c0, c1);
                 if (scale_a) p = pack_bf16x2(__uint_as_float(p << 16) * sa, __uint_as_float(p & 0xffff0000u) * sa);
-                if (scale_w) p = pack_bf16x2(__uint_as_float(p << 16) * sw, __uint_as_float(p & 0xffff0000u) * sw);
+                if (scale_w) p = pack_bf16x2(__uint_as_float(p << 16) * sw0, __uint_as_float(p & 0xffff0000u) * sw1);
                 return p;
             } else {
                 half2_t p = half2_t{(half_t)c0, (half_t)c1};
                 if (scale_a) p = p * half2_t{(half_t)sa, (half_t)sa};
-                if (scale_w) p = p * half2_t{(half_t)sw, (half_t)sw};
+                if (scale_w) p = p * half2_t{(half_t)sw0, (half_t)sw1};
                 return __builtin_bit_cast(uint32_t, p);
             }
         };
@@ -426,6 +441,15 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
         auto hi_f32 = [&](uint32_t p) { return ODT == BIE_BF16 ? __uint_as_float(p & 0xffff0000u) : f16_bits_to_f32(p >> 16); };
         const bool vec_ok = (N & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
         const int half = lane >> 5;
+        // scale_w of columns n .. n + 3 (n % 4 == 0): the scalar, or (CS) one 16-byte LDS read of the staged column scales
+        auto sw4 = [&](int n, float (&o)[4]) {
+            if constexpr (CS) {
+                const float4_t v = *reinterpret_cast<const float4_t*>(&csw[n - n_tile0]);
+                o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+            } else {
+                o[0] = o[1] = o[2] = o[3] = sw;
+            }
+        };
 #pragma unroll
         for (int i = 0; i < WM; i++) {
             const int m = (tile_m * AF + wy * WM + i) * 32 + m_l;
@@ -436,8 +460,12 @@ __global__ __launch_bounds__(256) void xnor_fp4_gemm_kernel(const uint8_t* __res
 #pragma unroll
                 for (int qp = 0; qp < 2; qp++) {
                     // registers 8qp .. 8qp+3: group 2qp (n + 4*half + e), 8qp+4 .. 8qp+7: group 2qp + 1
-                    const uint32_t p0 = fin2(acc[i][j][8 * qp], acc[i][j][8 * qp + 1]), p1 = fin2(acc[i][j][8 * qp + 2], acc[i][j][8 * qp + 3]);
-                    const uint32_t p2 = fin2(acc[i][j][8 * qp + 4], acc[i][j][8 * qp + 5]), p3 = fin2(acc[i][j][8 * qp + 6], acc[i][j][8 * qp + 7]);
+                    const int na = nb + 16 * qp + 4 * half, nc = na + 8;  // columns of registers 8qp and 8qp + 4
+                    float wa[4], wc[4];
+                    sw4(na, wa);
+                    sw4(nc, wc);
+                    const uint32_t p0 = fin2(acc[i][j][8 * qp], acc[i][j][8 * qp + 1], wa[0], wa[1]), p1 = fin2(acc[i][j][8 * qp + 2], acc[i][j][8 * qp + 3], wa[2], wa[3]);
+                    const uint32_t p2 = fin2(acc[i][j][8 * qp + 4], acc[i][j][8 * qp + 5], wc[0], wc[1]), p3 = fin2(acc[i][j][8 * qp + 6], acc[i][j][8 * qp + 7], wc[2], wc[3]);
                     if (vec_ok) {
                         const auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);  // first operand's upper half <-> second's lower half
                         const auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
@@ -478,7 +506,7 @@ int binary_fp4_image_values_launch(const void* v, const void* bias, uint8_t* ima
     return check_launch("fp4_image_values_kernel");
 }
 
-template <int ODT>
+template <int ODT, bool CS = false>
 static void fp4_gemm_launch_dt(const uint8_t* ximg, const uint8_t* wimg, void* y, long M, long N, long K, float scale, const void* sa, const void* sw,
                                int tile, hipStream_t st, int conv_p = 0) {
     const int KT = (int)fp4_k_tiles(K), RBA = (int)fp4_row_blocks(M), RBB = (int)fp4_row_blocks(N);
@@ -488,7 +516,7 @@ static void fp4_gemm_launch_dt(const uint8_t* ximg, const uint8_t* wimg, void* y
     // 256 x 256 tiles (one wave per SIMD, LDS reads at half the array's rate) once they fill most of the chip, else 128 x 128
     const bool big = tile == 256 || (tile != 128 && t256 >= 192);
 #define BIE_FP4_GO(WM_, VAR_, GRID_, TN_) \
-    hipLaunchKernelGGL((xnor_fp4_gemm_kernel<WM_, WM_, VAR_, ODT>), GRID_, dim3(256), 0, st, ximg, wimg, y, (int)M, (int)N, KT, RBA, RBB, TN_, scale, sa, sw, conv_p)
+    hipLaunchKernelGGL((xnor_fp4_gemm_kernel<WM_, WM_, VAR_, ODT, CS>), GRID_, dim3(256), 0, st, ximg, wimg, y, (int)M, (int)N, KT, RBA, RBB, TN_, scale, sa, sw, conv_p)
     if (big) {
         const int tn = (int)cdivl(N, 256);
         const dim3 grid((unsigned)t256);
@@ -505,7 +533,7 @@ static void fp4_gemm_launch_dt(const uint8_t* ximg, const uint8_t* wimg, void* y
     } else if (tile == 64 || (tile != 128 && cdivl(M, 128) * cdivl(N, 128) < 192)) {
         // mid M: 128 x 64 tiles (wave tile 64 x 32) double the workgroups when the 128 x 128 grid would leave CUs idle
         const int tn = (int)cdivl(N, 64);
-        hipLaunchKernelGGL((xnor_fp4_gemm_kernel<2, 1, 0, ODT>), dim3((unsigned)(cdivl(M, 128) * tn)), dim3(256), 0, st, ximg, wimg, y, (int)M, (int)N, KT, RBA, RBB, tn, scale, sa, sw, conv_p);
+        hipLaunchKernelGGL((xnor_fp4_gemm_kernel<2, 1, 0, ODT, CS>), dim3((unsigned)(cdivl(M, 128) * tn)), dim3(256), 0, st, ximg, wimg, y, (int)M, (int)N, KT, RBA, RBB, tn, scale, sa, sw, conv_p);
     } else {
         const int tn = (int)cdivl(N, 128);
         const dim3 grid((unsigned)(cdivl(M, 128) * tn));
@@ -525,6 +553,15 @@ int binary_fp4_gemm_launch(const uint8_t* ximg, const uint8_t* wimg, void* y, lo
     else if (dtype == BIE_BF16) fp4_gemm_launch_dt<BIE_BF16>(ximg, wimg, y, M, N, K, 1.0f, sa, sw, tile, st);
     else fp4_gemm_launch_dt<BIE_F32>(ximg, wimg, y, M, N, K, 1.0f, sa, sw, tile, st);
     return check_launch("xnor_fp4_gemm_kernel");
+}
+
+// the layer epilogue with a per-column scale_w [N] (the ternary layer's alpha): dtype 0 / 1 / 2, scale_a a device scalar or NULL
+int binary_fp4_gemm_colscale_launch(const uint8_t* ximg, const uint8_t* wimg, void* y, long M, long N, long K, const void* sa, const void* sw_vec, int dtype,
+                                    int tile, hipStream_t st) {
+    if (dtype == BIE_F16) fp4_gemm_launch_dt<BIE_F16, true>(ximg, wimg, y, M, N, K, 1.0f, sa, sw_vec, tile, st);
+    else if (dtype == BIE_BF16) fp4_gemm_launch_dt<BIE_BF16, true>(ximg, wimg, y, M, N, K, 1.0f, sa, sw_vec, tile, st);
+    else fp4_gemm_launch_dt<BIE_F32, true>(ximg, wimg, y, M, N, K, 1.0f, sa, sw_vec, tile, st);
+    return check_launch("xnor_fp4_gemm_kernel<colscale>");
 }
 
 // conv2d forward on the matrix pipe: x [B, C, H, W] -> channel-minor sign bits (ws head, binary.hip's pack_nhwc_bits) -> FP4 image of the

@@ -102,6 +102,15 @@ int unpack_u8_scaled_launch(const uint8_t* in, const float* scale, float* out, l
 int q4_pack_launch(const int32_t* in, int8_t* out, long n_out, hipStream_t st);
 int q4_unpack_launch(const int8_t* in, int32_t* out, long n_in, hipStream_t st);
 int q4_unpack_scale_launch(const int8_t* in, float* out, long n_in, float scale, hipStream_t st);
+// ternary.hip
+int ternary_pack_launch(const int8_t* trits, uint8_t* qweight, long N, long K, hipStream_t st);
+int ternary_unpack_launch(const uint8_t* qweight, int8_t* trits, long N, long K, hipStream_t st);
+int ternary_fp4_image_launch(const uint8_t* qweight, uint8_t* image, long N, long K, hipStream_t st);
+bool ternary_linear_fused_ok(long M, long N, long K);
+int ternary_linear_fused_launch(const void* x, const void* bias_a, const uint8_t* q, const void* sa, const void* alpha, void* y, long M, long N, long K,
+                                int dtype, int y_f32, hipStream_t st);
+int ternary_layer_fp4_launch(const uint8_t* ximg, const uint8_t* wimg, const void* sa, const void* alpha, void* y, long M, long N, long K, int dtype,
+                             hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -778,6 +787,64 @@ int bie_q4_conv2d_forward(const int8_t* a_packed, const int8_t* w_packed, void* 
     BIE_REQUIRE(need > 0, BIE_ERR_INVALID_ARG, "bie_q4_conv2d_forward: empty output");
     BIE_REQUIRE(workspace_bytes >= need, BIE_ERR_WORKSPACE, "bie_q4_conv2d_forward: workspace of %zu bytes required, got %zu", need, workspace_bytes);
     return q4_conv2d_launch(a_packed, w_packed, y, workspace, B, H, W, C, OC, ksize, stride, pad, dilation, scale_a, scale_w, dtype, as_stream(stream));
+}
+
+
+// ---------------------------------------------------------------------------------------------- ternary
+static int check_ternary_shape(const char* what, long N, long K) {
+    BIE_REQUIRE(N > 0 && N < (1L << 31) && K > 0 && K % 32 == 0 && K < (1L << 24), BIE_ERR_INVALID_ARG, "%s: N=%ld K=%ld (N >= 1, K %% 32 == 0, K < 2^24 required)",
+                what, N, K);
+    return BIE_OK;
+}
+
+int bie_ternary_pack(const int8_t* trits, uint8_t* qweight, long N, long K, void* stream) {
+    int rc = check_ternary_shape("bie_ternary_pack", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(trits && qweight, BIE_ERR_INVALID_ARG, "bie_ternary_pack: NULL pointer");
+    return ternary_pack_launch(trits, qweight, N, K, as_stream(stream));
+}
+
+int bie_ternary_unpack(const uint8_t* qweight, int8_t* trits, long N, long K, void* stream) {
+    int rc = check_ternary_shape("bie_ternary_unpack", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(trits && qweight, BIE_ERR_INVALID_ARG, "bie_ternary_unpack: NULL pointer");
+    return ternary_unpack_launch(qweight, trits, N, K, as_stream(stream));
+}
+
+int bie_ternary_fp4_image(const uint8_t* qweight, uint8_t* image, long N, long K, void* stream) {
+    int rc = check_ternary_shape("bie_ternary_fp4_image", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(qweight && image, BIE_ERR_INVALID_ARG, "bie_ternary_fp4_image: NULL pointer");
+    BIE_REQUIRE((reinterpret_cast<uintptr_t>(qweight) & 3) == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0, BIE_ERR_INVALID_ARG,
+                "bie_ternary_fp4_image: qweight must be 4-byte and image 16-byte aligned");
+    return ternary_fp4_image_launch(qweight, image, N, K, as_stream(stream));
+}
+
+int bie_ternary_linear_fused_ok(long M, long N, long K) { return ternary_linear_fused_ok(M, N, K) ? 1 : 0; }
+
+int bie_ternary_linear_fused(const void* x, const void* bias_a, const uint8_t* qweight, const void* scale_a, const void* alpha, void* y, long M, long N,
+                             long K, int dtype, int y_f32, void* stream) {
+    int rc = check_ternary_shape("bie_ternary_linear_fused", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_ternary_linear_fused: dtype %d", dtype);
+    BIE_REQUIRE(!y_f32 || (!scale_a && !alpha), BIE_ERR_INVALID_ARG, "bie_ternary_linear_fused: y_f32 (raw D) takes no scales");
+    BIE_REQUIRE(ternary_linear_fused_ok(M, N, K), BIE_ERR_UNSUPPORTED, "bie_ternary_linear_fused: M=%ld N=%ld K=%ld outside the one-launch range "
+                "(bie_ternary_linear_fused_ok)", M, N, K);
+    BIE_REQUIRE(x && qweight && y, BIE_ERR_INVALID_ARG, "bie_ternary_linear_fused: NULL tensor pointer");
+    BIE_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(bias_a)) & 15) == 0 && (reinterpret_cast<uintptr_t>(qweight) & 3) == 0,
+                BIE_ERR_INVALID_ARG, "bie_ternary_linear_fused: x and bias_a must be 16-byte aligned, qweight 4-byte aligned");
+    return ternary_linear_fused_launch(x, bias_a, qweight, scale_a, alpha, y, M, N, K, dtype, y_f32 ? 1 : 0, as_stream(stream));
+}
+
+int bie_ternary_linear_layer_fp4(const uint8_t* ximage, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, long M, long N, long K,
+                                 int dtype, void* stream) {
+    int rc = check_ternary_shape("bie_ternary_linear_layer_fp4", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(ximage && wimage && y && M > 0 && M < (1L << 31), BIE_ERR_INVALID_ARG, "bie_ternary_linear_layer_fp4: M=%ld", M);
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_ternary_linear_layer_fp4: dtype %d", dtype);
+    BIE_REQUIRE(((reinterpret_cast<uintptr_t>(ximage) | reinterpret_cast<uintptr_t>(wimage)) & 15) == 0, BIE_ERR_INVALID_ARG,
+                "bie_ternary_linear_layer_fp4: images must be 16-byte aligned");
+    return ternary_layer_fp4_launch(ximage, wimage, scale_a, alpha, y, M, N, K, dtype, as_stream(stream));
 }
 
 }  // extern "C"

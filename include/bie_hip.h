@@ -491,6 +491,31 @@ int bie_q4_conv2d_forward(const int8_t* a_packed, const int8_t* w_packed, void* 
                           int H, int W, int C, int OC, int ksize, int stride, int pad, int dilation, float scale_a, float scale_w,
                           int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------ ternary
+ * Ternary-weight / binary-activation linear layer (TernaryLinearCuda).  There is no reference implementation; these definitions are
+ * this library's own ("Ternary linear layer").
+ *   trits    [N, K] int8 in {-1, 0, +1} (pack: any positive value is +1, any negative one -1)
+ *   qweight  [2, N, K/8] uint8: plane 0 = non-zero mask, plane 1 = "value is +1" (a subset of plane 0); bit j of byte b holds
+ *            k = 8b + j (LSB first, the row packing of bie_binary_pack_rows_u8).  K % 32 == 0, N >= 1, K < 2^24.
+ *   D[m, n]  = sum_k t[n, k] * s[m, k] with s = +1 where (x + bias_a) >= 0 (sum rounded in the dtype), else -1: an exact integer.
+ *   y[m, n]  = dt( dt( dt(D) * scale_a ) * alpha[n] )   (dtype 0=f16 1=bf16 2=f32; scale_a a device scalar, alpha [N]; NULL = 1)
+ * bie_ternary_pack / bie_ternary_unpack: trits <-> qweight.
+ * bie_ternary_fp4_image: qweight -> FP4 (E2M1) image of the weights (+1 = 0x2, -1 = 0xA, 0 = 0x0) in the fragment order of
+ *   bie_binary_fp4_image, bie_binary_fp4_image_bytes(N, K) bytes, 16-byte aligned; built once per weight.
+ * bie_ternary_linear_fused_ok: 1 where the one-launch decode form is taken (small M; the bound was measured against the matrix-pipe form).
+ * bie_ternary_linear_fused: the whole layer in one launch (x, bias_a 16-byte aligned, qweight 4-byte aligned); y_f32 != 0: y is
+ *   float [M, N] = D with no rounding, and the scales must be NULL.
+ * bie_ternary_linear_layer_fp4: the same y from the x image of bie_binary_fp4_image_from_values(x, bias_a) and the weights' image,
+ *   on the matrix pipe, bit-identical to bie_ternary_linear_fused. */
+int bie_ternary_pack(const int8_t* trits, uint8_t* qweight, long N, long K, void* stream);
+int bie_ternary_unpack(const uint8_t* qweight, int8_t* trits, long N, long K, void* stream);
+int bie_ternary_fp4_image(const uint8_t* qweight, uint8_t* image, long N, long K, void* stream);
+int bie_ternary_linear_fused_ok(long M, long N, long K);
+int bie_ternary_linear_fused(const void* x, const void* bias_a, const uint8_t* qweight, const void* scale_a, const void* alpha, void* y,
+                             long M, long N, long K, int dtype, int y_f32, void* stream);
+int bie_ternary_linear_layer_fp4(const uint8_t* ximage, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, long M,
+                                 long N, long K, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
