@@ -1,1 +1,1 @@
-from .layer import TernaryLinearBase, ternarize
+from .layer import TernaryLinearBase, TernaryWeightState, ternarize

@@ -74,12 +74,6 @@ class TernaryLinearCuda(TernaryLinearBase):
         self.weight = None
         self._packed = True
 
-    def _init_scale_a(self, x: torch.Tensor) -> None:
-        # lazily initialised activation scale, as BinaryLinearCuda; the nonzero answer is remembered per version of the parameter
-        from bitorch_engine.extensions.q_linear_cuda import _cached
-        if not _cached(self.scale_a, "nonzero", lambda: bool(self.scale_a.is_nonzero())):
-            self.scale_a.data = ((2 if self.symmetric else 4) * x.abs().mean()).to(self.dtype)
-
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._check_forward(x)
         self._init_scale_a(x)

@@ -21,7 +21,37 @@ def ternarize(weight: torch.Tensor, threshold_factor: float = 0.7):
     return t, alpha, delta
 
 
-class TernaryLinearBase(nn.Module):
+class TernaryWeightState:
+    """The weight-state contract shared by the ternary layers (TernaryLinearBase, qconv's TernaryConv2dBase): a float latent `weight`, the
+    packed trits `qweight` and their per-output-channel scale `scale_w` (buffers), `bias_a` and `scale_a`.  A qweight-only checkpoint
+    carries no `weight`; loading one drops the latent weight, and loading a latent weight re-derives qweight before the next packed
+    forward.  Mixed in front of nn.Module; the layer sets `_packed` (qweight / scale_w hold the current weight)."""
+
+    def generate_quantized_weight(self, qweight_only: bool = False) -> None:
+        """Ternarise `weight` into qweight / scale_w; qweight_only: drop the float latent weight afterwards (a packed checkpoint)."""
+        self.prepare_params()
+        if qweight_only:
+            self.weight = None
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        # a qweight-only checkpoint carries no latent weight (and a latent weight may come into a layer that had dropped its own)
+        if prefix + "weight" in state_dict:
+            if self.weight is None:  # on the layer's device, whatever device the checkpoint tensor is on
+                self.weight = nn.Parameter(torch.empty(state_dict[prefix + "weight"].shape, dtype=self.dtype, device=self.bias_a.device))
+        elif self.weight is not None and prefix + "qweight" in state_dict:
+            self.weight = None
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        # with a latent weight, qweight is re-derived from it before the next packed forward
+        self._packed = self.weight is None
+
+    def _init_scale_a(self, x: torch.Tensor) -> None:
+        # lazily initialised activation scale (2 * mean|x|, 4 * when not symmetric); the nonzero answer is remembered per version of the parameter
+        from bitorch_engine.extensions.q_linear_cuda import _cached
+        if not _cached(self.scale_a, "nonzero", lambda: bool(self.scale_a.is_nonzero())):
+            self.scale_a.data = ((2 if self.symmetric else 4) * x.abs().mean()).to(self.dtype)
+
+
+class TernaryLinearBase(TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_ternary_weight),
     the packed trits `qweight` uint8 [2, N, K/8] and their per-row scale `scale_w` [N] (buffers), the learnable activation bias `bias_a` [K]
     and scale `scale_a` (initialised on the first forward to 2 * mean|x|, 4 * when not symmetric)."""
@@ -44,23 +74,6 @@ class TernaryLinearBase(nn.Module):
 
     def prepare_params(self) -> None:
         raise NotImplementedError("Subclasses should implement this method.")
-
-    def generate_quantized_weight(self, qweight_only: bool = False) -> None:
-        """Ternarise `weight` into qweight / scale_w; qweight_only: drop the float latent weight afterwards (a packed checkpoint)."""
-        self.prepare_params()
-        if qweight_only:
-            self.weight = None
-
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        # a qweight-only checkpoint carries no latent weight (and a latent weight may come into a layer that had dropped its own)
-        if prefix + "weight" in state_dict:
-            if self.weight is None:  # on the layer's device, whatever device the checkpoint tensor is on
-                self.weight = nn.Parameter(torch.empty(state_dict[prefix + "weight"].shape, dtype=self.dtype, device=self.bias_a.device))
-        elif self.weight is not None and prefix + "qweight" in state_dict:
-            self.weight = None
-        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
-        # with a latent weight, qweight is re-derived from it before the next packed forward
-        self._packed = self.weight is None
 
     def _check_forward(self, x: torch.Tensor) -> None:
         assert x.size(-1) == self.input_features, f"Weight and input tensor mismatch: {x.size(-1)} != {self.input_features}"

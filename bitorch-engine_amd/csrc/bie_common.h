@@ -114,6 +114,13 @@ template <> struct dt_traits<BIE_F32> {
     static constexpr int bytes = 4;
 };
 
+// The ternary layers' per-value epilogue: dt( dt( dt(d) * sa ) * sw ) in the layer dtype (a scale of 1.0 leaves its step exact).
+// ternary.hip's decode form and both one-launch ternary convs (binary_conv_fused.hip) round through this one function.
+template <int DT>
+__device__ __forceinline__ float layer_round(float d, float sa, float sw) {
+    return dt_traits<DT>::round(dt_traits<DT>::round(dt_traits<DT>::round(d) * sa) * sw);
+}
+
 // Every workspace starts with a 16 KiB head (zero on first use); every scratch user starts behind it.  Two protocols live in it
 // and must not share words: the first half holds split-K ARRIVAL TICKETS (one per 64-column output tile, returned to zero
 // by the last arriver: mpq_gemv.hip), the second half the tiles' GENERATION words of the tagged-granule reduction

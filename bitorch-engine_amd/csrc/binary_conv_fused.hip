@@ -67,6 +67,10 @@ struct ConvFusedArgs {
     int rpw, chunks, ocbs;  // output rows per workgroup, row chunks per image, workgroups per pixel range (64*G channels each)
     int IR, WP, PP;         // LDS image rows / columns (pixels), pitch of the [channel][pixel] sums
     float scale;
+    // ternary instances (TERN): wl = lane image of the non-zero mask plane, wl_pos that of the +1 plane; y in the dtype (y_f32: fp32 D)
+    const uint32_t* wl_pos;
+    const void *sa, *alpha;
+    int y_f32;
 };
 
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -82,8 +86,11 @@ __device__ __forceinline__ uint32_t xw_get(const typename xword<N>::type& v, int
     else return v[j];
 }
 
-// KS: kernel size (dilation 1); CWW: channel words per K quarter (C = 128 * CWW); G: 64-channel groups per lane; PXB: pixels per pass
-template <int KS, int CWW, int G, int PXB>
+// KS: kernel size (dilation 1); CWW: channel words per K quarter (C = 128 * CWW); G: 64-channel groups per lane; PXB: pixels per pass.
+// TERN: ternary weights (TernaryConv2dCuda): the mask and +1 words both sit in registers, the product is v_bcnt(mask & (pos ^ x)) -- one
+// VALU more per word -- and every wave adds nnz_q - 2 * popc for its K quarter, so the LDS sums are D itself (nnz_q: the popcount of the
+// wave's register-resident mask words, per lane = output channel; a zero border word is 32 times x = -1, as for the binary sum).
+template <int KS, int CWW, int G, int PXB, bool TERN = false>
 __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArgs a) {
     constexpr int T = KS * KS, CW = 4 * CWW, NWW = T * CWW;
     constexpr int PS = CW + 4;  // pixel pitch of the bit image in words: 16-byte aligned, and the pack phase's stores spread over the banks
@@ -108,12 +115,19 @@ __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArg
     asm volatile("" : "+s"(ybase), "+s"(yscale), "+s"(yoc), "+s"(ypitch), "+s"(yplane));
     // ---- 1. this wave's K quarter of the weights (requested first: in flight under the pack phase)
     uint32_t wreg[G][NWW];
+    uint32_t wpos[TERN ? G : 1][TERN ? NWW : 1];
 #pragma unroll
     for (int g = 0; g < G; g++) {
         const int blk = min(ocb * G + g, nblk - 1);  // a group beyond OC re-reads the last block: valid memory, never stored
-        const uint32_t* wp = a.wl + ((size_t)blk * 4 + wq) * (NWW * 64) + lane;
+        const size_t o = ((size_t)blk * 4 + wq) * (NWW * 64) + lane;
+        const uint32_t* wp = a.wl + o;
 #pragma unroll
         for (int i = 0; i < NWW; i++) wreg[g][i] = wp[i * 64];
+        if constexpr (TERN) {
+            const uint32_t* pp = a.wl_pos + o;
+#pragma unroll
+            for (int i = 0; i < NWW; i++) wpos[g][i] = pp[i * 64];
+        }
     }
 
     BIE_CONV_STAMP(1);
@@ -145,6 +159,15 @@ __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArg
     BIE_CONV_STAMP(2);
 
     // ---- 3. XNOR-popcount: PXB output pixels per pass, taps unrolled, x words by uniform-address LDS reads
+    int nnzq[TERN ? G : 1];  // TERN: non-zero weights of this lane's channel in this wave's K quarter
+    if constexpr (TERN) {
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            nnzq[g] = 0;
+#pragma unroll
+            for (int i = 0; i < NWW; i++) nnzq[g] += __builtin_popcount(wreg[g][i]);
+        }
+    }
     const uint32_t img_base = (uint32_t)(uintptr_t)(lds_u32*)img + (uint32_t)wq * (CWW * 4);  // LDS byte address of (row 0, col 0, this quarter)
     const uint32_t row_bytes = (uint32_t)a.WP * (PS * 4);
     int orow = 0, ocol = 0;  // output pixel p0 = (orow, ocol) inside the chunk
@@ -181,8 +204,13 @@ __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArg
 #pragma unroll
                     for (int j = 0; j < CWW; j++)
 #pragma unroll
-                        for (int g = 0; g < G; g++)
-                            asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc[g][i]) : "v"(xw_get<CWW>(xa[i], j) ^ wreg[g][(ti * KS + tj) * CWW + j]));
+                        for (int g = 0; g < G; g++) {
+                            const int wi = (ti * KS + tj) * CWW + j;
+                            if constexpr (TERN)
+                                asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc[g][i]) : "v"(wreg[g][wi] & (wpos[g][wi] ^ xw_get<CWW>(xa[i], j))));
+                            else
+                                asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc[g][i]) : "v"(xw_get<CWW>(xa[i], j) ^ wreg[g][wi]));
+                        }
             }
         }
         // ---- 4a. the four K quarters add up in LDS: red[group][channel][pixel]
@@ -190,7 +218,10 @@ __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArg
         for (int g = 0; g < G; g++)
 #pragma unroll
             for (int i = 0; i < PXB; i++)
-                if (p0 + i < P) __hip_atomic_fetch_add(red + (g * 64 + lane) * a.PP + p0 + i, acc[g][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (p0 + i < P) {
+                    if constexpr (TERN) __hip_atomic_fetch_add(red + (g * 64 + lane) * a.PP + p0 + i, nnzq[g] - 2 * acc[g][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    else __hip_atomic_fetch_add(red + (g * 64 + lane) * a.PP + p0 + i, acc[g][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
         ocol += PXB;
         while (ocol >= a.OW) { ocol -= a.OW; orow++; }
     }
@@ -201,6 +232,38 @@ __global__ __launch_bounds__(256) void xnor_conv_fused_kernel(const ConvFusedArg
     // ---- 4b. write-out, pixel-contiguous: row (group, channel) of `red` = P consecutive floats of y
     const int Kc = a.C * T;
     const __attribute__((address_space(3))) int* red3 = (const __attribute__((address_space(3))) int*)red;
+    if constexpr (TERN) {
+        // y = dt(dt(dt(D) * scale_a) * alpha[oc]) in the dtype (layer_round), or the fp32 D; a row (group, channel) is one output channel,
+        // so its alpha is one wave-uniform load per row
+        const long yoff = ((b * a.OC) * (long)a.OH + oh0) * a.OW;
+        auto wout = [&](auto dt_c) {
+            constexpr int DT = decltype(dt_c)::value;
+            const float sa = a.sa ? dt_traits<DT>::load(a.sa, 0) : 1.0f;
+            for (int row0 = wq * 4; row0 < G * 64; row0 += 16) {
+                float aw[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int row = row0 + r, oc = (ocb * G + (row >> 6)) * 64 + (row & 63);
+                    aw[r] = a.alpha ? dt_traits<DT>::load(a.alpha, min(oc, yoc - 1)) : 1.0f;
+                }
+                for (int p = lane; p < P; p += 64) {
+                    int pc[4];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) pc[r] = red3[(row0 + r) * ypitch + p];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int row = row0 + r, oc = (ocb * G + (row >> 6)) * 64 + (row & 63);
+                        if (oc < yoc) dt_traits<DT>::store(a.y, yoff + oc * yplane + p, layer_round<DT>((float)pc[r], sa, aw[r]));
+                    }
+                }
+            }
+        };
+        if (a.y_f32 || a.dtype == BIE_F32) wout(std::integral_constant<int, BIE_F32>{});
+        else if (a.dtype == BIE_F16) wout(std::integral_constant<int, BIE_F16>{});
+        else wout(std::integral_constant<int, BIE_BF16>{});
+        BIE_CONV_STAMP(5);
+        return;
+    }
     for (int row0 = wq * 4; row0 < G * 64; row0 += 16) {  // four rows per pass: their LDS reads and stores overlap
         for (int p = lane; p < P; p += 64) {
             int pc[4];
@@ -239,6 +302,9 @@ struct ConvMfmaArgs {
     int IR, WP, kb_per_row;
     float scale;
     int pitch;  // bytes per pixel of the LDS image: C / 2 + padding (a multiple of 16)
+    // ternary instances (TERN): wimg = the ternary FP4 image; alpha of the workgroup's 128 channels staged in LDS at byte alpha_off
+    const void *sa, *alpha;
+    int y_f32, alpha_off;
 };
 
 // 8 sign bits -> 8 E2M1 nibbles: bit 1 (value >= 0) -> 0x2 (+1.0), bit 0 -> 0xA (-1.0)  (= binary_fp4.hip::fp4_from_bits8)
@@ -290,7 +356,9 @@ __device__ __forceinline__ void conv_pixel_words(__amdgpu_buffer_rsrc_t rs, unsi
     }
 }
 
-template <int KS, int NPB, int CBT>  // CBT = C / 64: k steps per tap
+// TERN: the weight operand is the ternary FP4 image of the tap-major planes (+1 / -1 / 0 = 0x2 / 0xA / 0x0: bie_ternary_fp4_image), so the
+// accumulators hold the exact ternary sum D against the same -1-bordered sign image; only the epilogue differs (layer_round, alpha from LDS).
+template <int KS, int NPB, int CBT, bool TERN = false>  // CBT = C / 64: k steps per tap
 __global__ __launch_bounds__(256) void xnor_conv_mfma_kernel(const ConvMfmaArgs a) {
     constexpr int T = KS * KS;
     extern __shared__ __attribute__((aligned(16))) uint32_t conv_lds[];
@@ -337,6 +405,22 @@ __global__ __launch_bounds__(256) void xnor_conv_mfma_kernel(const ConvMfmaArgs 
         const int n16 = (int)((size_t)NIh * slot_pix * PITCH >> 4);
         uint4_t* i16 = reinterpret_cast<uint4_t*>(conv_lds);
         for (int i = tid; i < n16; i += 256) i16[i] = uint4_t{0xaaaaaaaau, 0xaaaaaaaau, 0xaaaaaaaau, 0xaaaaaaaau};
+    }
+    // TERN: scale_a is read here, before the k loop, into a register the loop cannot release: loaded in the epilogue, its pending vector
+    // load made every conditional store there wait for vmcnt(0) -- stores included -- and the fp32 epilogue ran 1.5 x the binary kernel
+    float sa = 1.0f;
+    if constexpr (TERN) {
+        if (a.sa) sa = a.dtype == BIE_F16 ? dt_traits<BIE_F16>::load(a.sa, 0) : a.dtype == BIE_BF16 ? dt_traits<BIE_BF16>::load(a.sa, 0)
+                                                                                                   : dt_traits<BIE_F32>::load(a.sa, 0);
+        asm volatile("" : "+v"(sa));
+    }
+    if constexpr (TERN) {  // the workgroup's 128 alphas, once (channels past OC repeat the last one: never stored)
+        float* as = reinterpret_cast<float*>(img + a.alpha_off);
+        if (tid < 128) {
+            const int oc = min(ocb * 128 + tid, a.OC - 1);
+            as[tid] = !a.alpha ? 1.0f : a.dtype == BIE_F16 ? dt_traits<BIE_F16>::load(a.alpha, oc)
+                                      : a.dtype == BIE_BF16 ? dt_traits<BIE_BF16>::load(a.alpha, oc) : dt_traits<BIE_F32>::load(a.alpha, oc);
+        }
     }
     __syncthreads();
     const int ia = max(ih_lo, 0), ib = min(ih_lo + IRn, a.H);  // input rows of the picture this workgroup needs
@@ -486,6 +570,35 @@ __global__ __launch_bounds__(256) void xnor_conv_mfma_kernel(const ConvMfmaArgs 
     // ---- 4. y[b][oc][oh0 * OW + p]: lanes 0..31 of a register = 32 consecutive pixels of one output channel
     const long plane = (long)a.OH * a.OW;
     const int oc0 = ocb * 128 + wave * 32 + 4 * (lane >> 5);
+    if constexpr (TERN) {
+        // y = dt(dt(dt(D) * scale_a) * alpha[oc]) (layer_round) or the fp32 D; the 16 alphas of a lane: four 16-byte LDS reads
+        const float4_t* as4 = reinterpret_cast<const float4_t*>(img + a.alpha_off) + ((oc0 - ocb * 128) >> 2);
+        float aw[16];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float4_t v = as4[2 * q];
+            aw[4 * q] = v.x; aw[4 * q + 1] = v.y; aw[4 * q + 2] = v.z; aw[4 * q + 3] = v.w;
+        }
+        auto wout = [&](auto dt_c) {
+            constexpr int DT = decltype(dt_c)::value;
+#pragma unroll
+            for (int pb = 0; pb < NPB; pb++) {
+                if (pslot[pb] < 0) continue;
+                const long yo = ((long)(b0 + pslot[pb]) * a.OC) * plane + (long)oh0 * a.OW + ppix[pb];
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    const int oc = oc0 + 8 * (i >> 2) + (i & 3);
+                    const float d = NACC == 2 ? acc[0][pb][i] + acc[NACC - 1][pb][i] : acc[0][pb][i];
+                    if (oc < a.OC) dt_traits<DT>::store(a.y, yo + oc * plane, layer_round<DT>(d, sa, aw[i]));
+                }
+            }
+        };
+        if (a.y_f32 || a.dtype == BIE_F32) wout(std::integral_constant<int, BIE_F32>{});
+        else if (a.dtype == BIE_F16) wout(std::integral_constant<int, BIE_F16>{});
+        else wout(std::integral_constant<int, BIE_BF16>{});
+        BIE_CONV_STAMP(5);
+        return;
+    }
 #pragma unroll
     for (int pb = 0; pb < NPB; pb++) {
         if (pslot[pb] < 0) continue;
@@ -516,7 +629,9 @@ __global__ __launch_bounds__(256) void conv_weight_lanes_kernel(const uint32_t* 
 
 struct ConvFusedPlan { int G, rpw, chunks, ocbs, IR, WP, PP, pxb; size_t lds; };
 
-bool conv_fused_plan(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil, ConvFusedPlan* out) {
+// tern: the ternary instances hold two weight planes in registers: G = 2 only while its 2 * 2 * T * CWW weight words are no more than the
+// binary maximum (72 at C = 512, k = 3, G = 2) -- the 3 x 3 convolutions over 512 channels run with G = 1
+bool conv_fused_plan(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil, ConvFusedPlan* out, bool tern = false) {
     if (!(ks == 1 || ks == 3) || dil != 1 || !(C == 128 || C == 256 || C == 512) || B < 1 || OC < 1 || stride < 1 || pad < 0) return false;
     const int OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1, OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
     if (OH < 1 || OW < 1 || OW > 64) return false;
@@ -526,6 +641,7 @@ bool conv_fused_plan(int B, int C, int H, int W, int OC, int ks, int stride, int
     const int rmax = 64 / OW;  // output pixels of a workgroup live in 64 lanes at write-out
     auto wgs = [&](int G, int rpw) { return (long)B * cdiv(OC, 64 * G) * cdiv(OH, rpw); };
     p.G = (OC > 64 && wgs(2, min(rmax, OH)) >= 256) ? 2 : 1;
+    if (tern && 2 * 2 * ks * ks * (C / 128) > 72) p.G = 1;
     p.ocbs = cdiv(OC, 64 * p.G);
     // at least ~512 workgroups when the problem has them, whole output rows per workgroup, as many rows as still give that
     int rpw = min(rmax, OH);
@@ -549,7 +665,8 @@ int conv_mfma_pitch_pad() {
     return pad;
 }
 
-bool conv_mfma_plan(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil, ConvMfmaPlan* out) {
+// extra: LDS bytes behind the image (the ternary instances' 128 staged alphas)
+bool conv_mfma_plan(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil, ConvMfmaPlan* out, size_t extra = 0) {
     if (!(ks == 1 || ks == 3) || dil != 1 || !(C == 64 || C == 128 || C == 256 || C == 512) || B < 1 || OC < 1 || stride < 1 || pad < 0) return false;
     const int OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1, OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
     if (OH < 1 || OW < 1 || OW > 128) return false;
@@ -576,9 +693,78 @@ bool conv_mfma_plan(int B, int C, int H, int W, int OC, int ks, int stride, int 
         p.IR = (p.rpw - 1) * stride + ks;
     }
     p.lds = (size_t)p.ni * p.IR * p.WP * pitch;
-    if (p.lds > 64 * 1024) return false;
+    if (p.lds + extra > 64 * 1024) return false;
     *out = p;
     return true;
+}
+
+constexpr size_t TERN_ALPHA_BYTES = 128 * 4;  // the ternary matrix-pipe instances' staged alphas, behind the LDS image
+
+template <bool TERN>
+void conv_mfma_dispatch(const ConvMfmaArgs& a, const ConvMfmaPlan& p, int ks, int C, unsigned grid, size_t lds, hipStream_t st) {
+    const int cbt = C / 64;
+#define BIE_CM3(KSV, NPBV, CBV) hipLaunchKernelGGL((xnor_conv_mfma_kernel<KSV, NPBV, CBV, TERN>), dim3(grid), dim3(256), lds, st, a)
+#define BIE_CM2(KSV, NPBV) do { if (cbt == 8) BIE_CM3(KSV, NPBV, 8); else if (cbt == 4) BIE_CM3(KSV, NPBV, 4); else if (cbt == 2) BIE_CM3(KSV, NPBV, 2); else BIE_CM3(KSV, NPBV, 1); } while (0)
+    if (ks == 3) { if (p.npb == 4) BIE_CM2(3, 4); else BIE_CM2(3, 2); }
+    else { if (p.npb == 4) BIE_CM2(1, 4); else BIE_CM2(1, 2); }
+#undef BIE_CM2
+#undef BIE_CM3
+}
+
+template <int KS, int CWW, int G, bool TERN>
+void conv_fused_px(const ConvFusedArgs& a, const ConvFusedPlan& p, unsigned grid, hipStream_t st) {
+    if (p.pxb == 7) hipLaunchKernelGGL((xnor_conv_fused_kernel<KS, CWW, G, 7, TERN>), dim3(grid), dim3(256), p.lds, st, a);
+    else hipLaunchKernelGGL((xnor_conv_fused_kernel<KS, CWW, G, 8, TERN>), dim3(grid), dim3(256), p.lds, st, a);
+}
+
+template <int KS, int CWW, bool TERN>
+void conv_fused_g(const ConvFusedArgs& a, const ConvFusedPlan& p, unsigned grid, hipStream_t st) {
+    constexpr bool g2 = !TERN || 2 * 2 * KS * KS * CWW <= 72;  // the ternary plan's cap (conv_fused_plan): no instance beyond it
+    if constexpr (g2) {
+        if (p.G == 2) return conv_fused_px<KS, CWW, 2, TERN>(a, p, grid, st);
+    }
+    conv_fused_px<KS, CWW, 1, TERN>(a, p, grid, st);
+}
+
+template <bool TERN>
+void conv_fused_dispatch(const ConvFusedArgs& a, const ConvFusedPlan& p, int ks, int C, unsigned grid, hipStream_t st) {
+    const int cww = C / 128;
+    if (ks == 3) {
+        if (cww == 4) conv_fused_g<3, 4, TERN>(a, p, grid, st); else if (cww == 2) conv_fused_g<3, 2, TERN>(a, p, grid, st); else conv_fused_g<3, 1, TERN>(a, p, grid, st);
+    } else {
+        if (cww == 4) conv_fused_g<1, 4, TERN>(a, p, grid, st); else if (cww == 2) conv_fused_g<1, 2, TERN>(a, p, grid, st); else conv_fused_g<1, 1, TERN>(a, p, grid, st);
+    }
+}
+
+ConvMfmaArgs mfma_args(const void* x, const uint8_t* wimg, void* y, int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dtype,
+                       const ConvMfmaPlan& p) {
+    ConvMfmaArgs a{};
+    a.x = x; a.wimg = wimg; a.y = (float*)y;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.OC = OC;
+    a.OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1;
+    a.OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
+    a.stride = stride; a.pad = pad; a.dtype = dtype;
+    a.ni = p.ni; a.rpw = p.rpw; a.chunks = p.chunks; a.ocbs = p.ocbs; a.IR = p.IR; a.WP = p.WP;
+    a.kb_per_row = 2 * cdiv(ks * ks * C, 128);
+    a.pitch = p.pitch;
+    return a;
+}
+
+ConvFusedArgs fused_args(const void* x, const uint32_t* wl, void* y, int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dtype,
+                         const ConvFusedPlan& p) {
+    ConvFusedArgs a{};
+    a.x = x; a.wl = wl; a.y = (float*)y;
+    a.B = B; a.C = C; a.H = H; a.W = W; a.OC = OC;
+    a.OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1;
+    a.OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
+    a.stride = stride; a.pad = pad; a.dtype = dtype;
+    a.rpw = p.rpw; a.chunks = p.chunks; a.ocbs = p.ocbs; a.IR = p.IR; a.WP = p.WP; a.PP = p.PP;
+    return a;
+}
+
+unsigned mfma_grid(int B, const ConvMfmaPlan& p) {
+    const long groups = p.chunks == 1 ? cdiv(B, p.ni) : (long)B * p.chunks;
+    return (unsigned)(groups * p.ocbs);
 }
 
 }  // namespace
@@ -595,25 +781,9 @@ int binary_conv_mfma_launch(const void* x, const uint8_t* wimg, float* y, int B,
         set_error("bie_binary_conv2d_forward_mfma: geometry outside the one-launch matrix-pipe form (k in {1, 3}, dilation 1, C in {64, 128, 256, 512}, OW <= 128)");
         return BIE_ERR_UNSUPPORTED;
     }
-    ConvMfmaArgs a;
-    a.x = x; a.wimg = wimg; a.y = y;
-    a.B = B; a.C = C; a.H = H; a.W = W; a.OC = OC;
-    a.OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1;
-    a.OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
-    a.stride = stride; a.pad = pad; a.dtype = dtype;
-    a.ni = p.ni; a.rpw = p.rpw; a.chunks = p.chunks; a.ocbs = p.ocbs; a.IR = p.IR; a.WP = p.WP;
-    a.kb_per_row = 2 * cdiv(ks * ks * C, 128);
+    ConvMfmaArgs a = mfma_args(x, wimg, y, B, C, H, W, OC, ks, stride, pad, dtype, p);
     a.scale = scale;
-    a.pitch = p.pitch;
-    const long groups = p.chunks == 1 ? cdiv(B, p.ni) : (long)B * p.chunks;
-    const unsigned grid = (unsigned)(groups * p.ocbs);
-    const int cbt = C / 64;
-#define BIE_CM3(KSV, NPBV, CBV) hipLaunchKernelGGL((xnor_conv_mfma_kernel<KSV, NPBV, CBV>), dim3(grid), dim3(256), p.lds, st, a)
-#define BIE_CM2(KSV, NPBV) do { if (cbt == 8) BIE_CM3(KSV, NPBV, 8); else if (cbt == 4) BIE_CM3(KSV, NPBV, 4); else if (cbt == 2) BIE_CM3(KSV, NPBV, 2); else BIE_CM3(KSV, NPBV, 1); } while (0)
-    if (ks == 3) { if (p.npb == 4) BIE_CM2(3, 4); else BIE_CM2(3, 2); }
-    else { if (p.npb == 4) BIE_CM2(1, 4); else BIE_CM2(1, 2); }
-#undef BIE_CM2
-#undef BIE_CM3
+    conv_mfma_dispatch<false>(a, p, ks, C, mfma_grid(B, p), p.lds, st);
     return check_launch("xnor_conv_mfma_kernel");
 }
 
@@ -637,26 +807,58 @@ int binary_conv_fused_launch(const void* x, const uint32_t* wl, float* y, int B,
         set_error("bie_binary_conv2d_forward_fused: geometry outside the one-launch form (k in {1, 3}, dilation 1, C in {128, 256, 512}, OW <= 64)");
         return BIE_ERR_UNSUPPORTED;
     }
-    ConvFusedArgs a;
-    a.x = x; a.wl = wl; a.y = y;
-    a.B = B; a.C = C; a.H = H; a.W = W; a.OC = OC;
-    a.OH = (H + 2 * pad - (ks - 1) - 1) / stride + 1;
-    a.OW = (W + 2 * pad - (ks - 1) - 1) / stride + 1;
-    a.stride = stride; a.pad = pad; a.dtype = dtype;
-    a.rpw = p.rpw; a.chunks = p.chunks; a.ocbs = p.ocbs; a.IR = p.IR; a.WP = p.WP; a.PP = p.PP;
+    ConvFusedArgs a = fused_args(x, wl, y, B, C, H, W, OC, ks, stride, pad, dtype, p);
     a.scale = scale;
-    const unsigned grid = (unsigned)((long)B * p.chunks * p.ocbs);
-    const int cww = C / 128;
-#define BIE_CF4(KSV, CWWV, GV, PXV) hipLaunchKernelGGL((xnor_conv_fused_kernel<KSV, CWWV, GV, PXV>), dim3(grid), dim3(256), p.lds, st, a)
-#define BIE_CF3(KSV, CWWV, GV) do { if (p.pxb == 7) BIE_CF4(KSV, CWWV, GV, 7); else BIE_CF4(KSV, CWWV, GV, 8); } while (0)
-#define BIE_CF2(KSV, CWWV) do { if (p.G == 2) BIE_CF3(KSV, CWWV, 2); else BIE_CF3(KSV, CWWV, 1); } while (0)
-#define BIE_CF1(KSV) do { if (cww == 4) BIE_CF2(KSV, 4); else if (cww == 2) BIE_CF2(KSV, 2); else BIE_CF2(KSV, 1); } while (0)
-    if (ks == 3) BIE_CF1(3); else BIE_CF1(1);
-#undef BIE_CF1
-#undef BIE_CF2
-#undef BIE_CF3
-#undef BIE_CF4
+    conv_fused_dispatch<false>(a, p, ks, C, (unsigned)((long)B * p.chunks * p.ocbs), st);
     return check_launch("xnor_conv_fused_kernel");
+}
+
+// ---- ternary conv2d (TernaryConv2dCuda): the two one-launch forms with TERN = true, and the one host-side choice between them -------------
+// The VALU form serves up to this many output pixels (B * OH * OW) where both forms can run; beyond it the matrix-pipe form.  Measured on the
+// MI355X with the ternary kernels on the ResNet-18 stages (tools/ternary_conv_bench.py, profiles/ternary_conv_bench.jsonl, fp16 / bf16):
+// the VALU form is ahead at 49 - 784 pixels except 512 -> 512 on 7 x 7 at B = 8 (392: 16.4 against 15.8 us), and at 1568 pixels it is
+// ahead on three shapes by 3 - 6 us (256 on 14 x 14, 128 -> 256 stride 2, both k) and behind on three by 7 - 15 us (512 on 7 x 7 at
+// B = 32, 256 -> 512 stride 2, both k); at 6272 and beyond the matrix pipe is ahead on every shape.  784 keeps the least lost time.
+constexpr long TERN_CONV_VALU_MAX_PIXELS = 784;
+
+int ternary_conv2d_form(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil) {
+    if (B < 1 || C < 1 || H < 1 || W < 1 || OC < 1 || ks < 1 || stride < 1 || pad < 0 || dil < 1 || C % 32) return 0;
+    if ((long)ks * ks * C >= (1L << 24) || (long)B * C * H * W >= (1L << 31) || (long)B * OC * H * W >= (1L << 31)) return 0;
+    const long OH = (H + 2L * pad - (long)dil * (ks - 1) - 1) / stride + 1, OW = (W + 2L * pad - (long)dil * (ks - 1) - 1) / stride + 1;
+    if (OH < 1 || OW < 1) return 0;
+    ConvFusedPlan fp;
+    ConvMfmaPlan mp;
+    const bool valu = conv_fused_plan(B, C, H, W, OC, ks, stride, pad, dil, &fp, true);
+    const bool mfma = conv_mfma_plan(B, C, H, W, OC, ks, stride, pad, dil, &mp, TERN_ALPHA_BYTES);
+    if (valu && (!mfma || (long)B * OH * OW <= TERN_CONV_VALU_MAX_PIXELS)) return 1;
+    return mfma ? 2 : 0;
+}
+
+int ternary_conv_fused_launch(const void* x, const uint32_t* wl_mask, const uint32_t* wl_pos, const void* sa, const void* alpha, void* y, int B, int C,
+                              int H, int W, int OC, int ks, int stride, int pad, int dil, int dtype, int y_f32, hipStream_t st) {
+    ConvFusedPlan p;
+    if (!conv_fused_plan(B, C, H, W, OC, ks, stride, pad, dil, &p, true)) {
+        set_error("bie_ternary_conv2d_forward_fused: geometry outside the one-launch VALU form (k in {1, 3}, dilation 1, C in {128, 256, 512}, OW <= 64)");
+        return BIE_ERR_UNSUPPORTED;
+    }
+    ConvFusedArgs a = fused_args(x, wl_mask, y, B, C, H, W, OC, ks, stride, pad, dtype, p);
+    a.wl_pos = wl_pos; a.sa = sa; a.alpha = alpha; a.y_f32 = y_f32;
+    conv_fused_dispatch<true>(a, p, ks, C, (unsigned)((long)B * p.chunks * p.ocbs), st);
+    return check_launch("xnor_conv_fused_kernel<ternary>");
+}
+
+int ternary_conv_mfma_launch(const void* x, const uint8_t* wimg, const void* sa, const void* alpha, void* y, int B, int C, int H, int W, int OC, int ks,
+                             int stride, int pad, int dil, int dtype, int y_f32, hipStream_t st) {
+    ConvMfmaPlan p;
+    if (!conv_mfma_plan(B, C, H, W, OC, ks, stride, pad, dil, &p, TERN_ALPHA_BYTES)) {
+        set_error("bie_ternary_conv2d_forward_mfma: geometry outside the one-launch matrix-pipe form (k in {1, 3}, dilation 1, C in {64, 128, 256, 512}, "
+                  "OW <= 128, the input rows' image in 64 KiB of LDS)");
+        return BIE_ERR_UNSUPPORTED;
+    }
+    ConvMfmaArgs a = mfma_args(x, wimg, y, B, C, H, W, OC, ks, stride, pad, dtype, p);
+    a.sa = sa; a.alpha = alpha; a.y_f32 = y_f32; a.alpha_off = (int)p.lds;  // p.lds: a multiple of the 16-byte pitch
+    conv_mfma_dispatch<true>(a, p, ks, C, mfma_grid(B, p), p.lds + TERN_ALPHA_BYTES, st);
+    return check_launch("xnor_conv_mfma_kernel<ternary>");
 }
 
 #ifdef BIE_CONV_LAB

@@ -85,6 +85,11 @@ int binary_conv_fused_launch(const void* x, const uint32_t* wl, float* y, int B,
 bool binary_conv_mfma_ok(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil);
 int binary_conv_mfma_launch(const void* x, const uint8_t* wimg, float* y, int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil,
                             float scale, int dtype, hipStream_t st);
+int ternary_conv2d_form(int B, int C, int H, int W, int OC, int ks, int stride, int pad, int dil);
+int ternary_conv_fused_launch(const void* x, const uint32_t* wl_mask, const uint32_t* wl_pos, const void* sa, const void* alpha, void* y, int B, int C,
+                              int H, int W, int OC, int ks, int stride, int pad, int dil, int dtype, int y_f32, hipStream_t st);
+int ternary_conv_mfma_launch(const void* x, const uint8_t* wimg, const void* sa, const void* alpha, void* y, int B, int C, int H, int W, int OC, int ks,
+                             int stride, int pad, int dil, int dtype, int y_f32, hipStream_t st);
 size_t binary_fp4_image_bytes(long rows, long K);
 int binary_fp4_image_launch(const uint8_t* rowpacked, uint8_t* image, long rows, long K, hipStream_t st);
 int binary_fp4_image_values_launch(const void* v, const void* bias, uint8_t* image, long rows, long K, int dtype, hipStream_t st);
@@ -845,6 +850,48 @@ int bie_ternary_linear_layer_fp4(const uint8_t* ximage, const uint8_t* wimage, c
     BIE_REQUIRE(((reinterpret_cast<uintptr_t>(ximage) | reinterpret_cast<uintptr_t>(wimage)) & 15) == 0, BIE_ERR_INVALID_ARG,
                 "bie_ternary_linear_layer_fp4: images must be 16-byte aligned");
     return ternary_layer_fp4_launch(ximage, wimage, scale_a, alpha, y, M, N, K, dtype, as_stream(stream));
+}
+
+
+// ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.
+int bie_ternary_conv2d_form(int B, int C, int H, int W, int OC, int ksize, int stride, int pad, int dilation) {
+    return ternary_conv2d_form(B, C, H, W, OC, ksize, stride, pad, dilation);
+}
+
+static int check_ternary_conv(const char* what, const void* x, const void* y, const void* sa, const void* alpha, int B, int C, int H, int W, int OC,
+                              int ksize, int stride, int pad, int dilation, int dtype, int y_f32) {
+    BIE_REQUIRE(x && y, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", what);
+    BIE_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && OC > 0 && ksize > 0 && stride > 0 && dilation > 0 && pad >= 0, BIE_ERR_INVALID_ARG, "%s: bad geometry",
+                what);
+    BIE_REQUIRE((H + 2L * pad - (long)dilation * (ksize - 1) - 1) / stride + 1 > 0 && (W + 2L * pad - (long)dilation * (ksize - 1) - 1) / stride + 1 > 0,
+                BIE_ERR_INVALID_ARG, "%s: empty output", what);
+    BIE_REQUIRE(C % 32 == 0, BIE_ERR_INVALID_ARG, "%s: C=%d must be a multiple of 32", what, C);
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "%s: dtype %d", what, dtype);
+    BIE_REQUIRE(!y_f32 || (!sa && !alpha), BIE_ERR_INVALID_ARG, "%s: y_f32 (raw D) takes no scales", what);
+    BIE_REQUIRE((long)ksize * ksize * C < (1L << 24), BIE_ERR_UNSUPPORTED, "%s: C*k*k=%ld beyond the exact range of the fp32 accumulator (2^24)", what,
+                (long)ksize * ksize * C);
+    BIE_REQUIRE((long)B * C * H * W < (1L << 31) && (long)B * OC * H * W < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: tensor beyond 2^31 elements", what);
+    return BIE_OK;
+}
+
+int bie_ternary_conv2d_forward_fused(const void* x, const uint32_t* wlanes_mask, const uint32_t* wlanes_pos, const void* scale_a, const void* alpha, void* y,
+                                     int B, int C, int H, int W, int OC, int ksize, int stride, int pad, int dilation, int dtype, int y_f32, void* stream) {
+    int rc = check_ternary_conv("bie_ternary_conv2d_forward_fused", x, y, scale_a, alpha, B, C, H, W, OC, ksize, stride, pad, dilation, dtype, y_f32);
+    if (rc) return rc;
+    BIE_REQUIRE(wlanes_mask && wlanes_pos, BIE_ERR_INVALID_ARG, "bie_ternary_conv2d_forward_fused: NULL weight image");
+    BIE_REQUIRE(((reinterpret_cast<uintptr_t>(wlanes_mask) | reinterpret_cast<uintptr_t>(wlanes_pos)) & 15) == 0, BIE_ERR_INVALID_ARG,
+                "bie_ternary_conv2d_forward_fused: the lane images must be 16-byte aligned");
+    return ternary_conv_fused_launch(x, wlanes_mask, wlanes_pos, scale_a, alpha, y, B, C, H, W, OC, ksize, stride, pad, dilation, dtype, y_f32 ? 1 : 0,
+                                     as_stream(stream));
+}
+
+int bie_ternary_conv2d_forward_mfma(const void* x, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, int B, int C, int H, int W,
+                                    int OC, int ksize, int stride, int pad, int dilation, int dtype, int y_f32, void* stream) {
+    int rc = check_ternary_conv("bie_ternary_conv2d_forward_mfma", x, y, scale_a, alpha, B, C, H, W, OC, ksize, stride, pad, dilation, dtype, y_f32);
+    if (rc) return rc;
+    BIE_REQUIRE(wimage, BIE_ERR_INVALID_ARG, "bie_ternary_conv2d_forward_mfma: NULL weight image");
+    BIE_REQUIRE((reinterpret_cast<uintptr_t>(wimage) & 15) == 0, BIE_ERR_INVALID_ARG, "bie_ternary_conv2d_forward_mfma: the weight image must be 16-byte aligned");
+    return ternary_conv_mfma_launch(x, wimage, scale_a, alpha, y, B, C, H, W, OC, ksize, stride, pad, dilation, dtype, y_f32 ? 1 : 0, as_stream(stream));
 }
 
 }  // extern "C"

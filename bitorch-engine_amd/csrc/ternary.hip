@@ -179,10 +179,7 @@ __global__ __launch_bounds__(256) void ternary_fused_kernel(const void* __restri
                     if (y_f32) {
                         ((float*)y)[(long)r * N + n] = v;
                     } else {
-                        v = dt_traits<DT>::round(v);
-                        if (scale_a) v = dt_traits<DT>::round(v * sa);
-                        if (alpha) v = dt_traits<DT>::round(v * aw);
-                        dt_traits<DT>::store(y, (long)r * N + n, v);
+                        dt_traits<DT>::store(y, (long)r * N + n, layer_round<DT>(v, sa, aw));  // sa / aw are 1.0 where NULL
                     }
                 }
             }

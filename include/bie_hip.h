@@ -516,6 +516,25 @@ int bie_ternary_linear_fused(const void* x, const void* bias_a, const uint8_t* q
 int bie_ternary_linear_layer_fp4(const uint8_t* ximage, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, long M,
                                  long N, long K, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------ ternary conv
+ * Ternary-weight / binary-activation conv2d (TernaryConv2dCuda; INTEGRATION.md, "Ternary conv2d layer").  No reference implementation.
+ *   x        [B, C, H, W] (dtype 0=f16 1=bf16 2=f32): the activations after the bias add; s = +1 where x >= 0 (NaN: -1), padding s = -1
+ *   qweight  the linear's [2, OC, C*k*k/8] over the OIHW flatten order k = c*k*k + kh*k + kw (C % 32 == 0, C*k*k < 2^24)
+ *   D        [b, oc, oh, ow] = sum_{c,kh,kw} t[oc, c, kh, kw] * s[b, c, oh*stride - pad + kh*dil, ow*stride - pad + kw*dil]  (exact)
+ *   y        = dt( dt( dt(D) * scale_a ) * alpha[oc] ) in the dtype (scale_a a device scalar, alpha [OC]; NULL = 1), or with y_f32 the
+ *              fp32 D (scales NULL)
+ * bie_ternary_conv2d_form: the ONE place that decides the form: 1 = VALU one-launch (bie_ternary_conv2d_forward_fused), 2 = matrix-pipe
+ *   one-launch (bie_ternary_conv2d_forward_mfma), 0 = neither (the caller's general path: unfold + the ternary linear).  Host only.
+ * bie_ternary_conv2d_forward_fused: wlanes_mask / wlanes_pos = bie_binary_conv_weight_lanes of bie_binary_conv_weight_taps of plane 0 / 1
+ *   (16-byte aligned).  bie_ternary_conv2d_forward_mfma: wimage = bie_ternary_fp4_image of the two tap-major planes stacked as
+ *   [2, OC, k*k*C/8] (rows OC, K = k*k*C; 16-byte aligned).  Both are stream-ordered, need no workspace, validate every argument before
+ *   any device call and return BIE_ERR_UNSUPPORTED for a geometry outside their form.  Bit-identical to each other. */
+int bie_ternary_conv2d_form(int B, int C, int H, int W, int OC, int ksize, int stride, int pad, int dilation);
+int bie_ternary_conv2d_forward_fused(const void* x, const uint32_t* wlanes_mask, const uint32_t* wlanes_pos, const void* scale_a, const void* alpha, void* y,
+                                     int B, int C, int H, int W, int OC, int ksize, int stride, int pad, int dilation, int dtype, int y_f32, void* stream);
+int bie_ternary_conv2d_forward_mfma(const void* x, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, int B, int C, int H, int W,
+                                    int OC, int ksize, int stride, int pad, int dilation, int dtype, int y_f32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
