@@ -1,1 +1,1 @@
-from .layer import TernaryLinearBase, TernaryWeightState, ternarize
+from .layer import TernaryLinearBase, TernaryWeightState, ternarize, ternarize_absmean

@@ -21,6 +21,15 @@ def ternarize(weight: torch.Tensor, threshold_factor: float = 0.7):
     return t, alpha, delta
 
 
+def ternarize_absmean(weight: torch.Tensor):
+    """BitNet b1.58 absmean rule, per tensor, in fp32:  beta = max(mean |W|, 1e-5);  t = clamp(rint(W / beta), -1, 1);  alpha_n = beta for
+    every row n.  -> (trits int8 [N, K], alpha fp32 [N])."""
+    w = weight.detach().float()
+    beta = w.abs().mean().clamp(min=1e-5)
+    t = torch.round(w / beta).clamp(-1, 1).to(torch.int8)
+    return t, beta.expand(w.shape[0]).clone()
+
+
 class TernaryWeightState:
     """The weight-state contract shared by the ternary layers (TernaryLinearBase, qconv's TernaryConv2dBase): a float latent `weight`, the
     packed trits `qweight` and their per-output-channel scale `scale_w` (buffers), `bias_a` and `scale_a`.  A qweight-only checkpoint
@@ -37,12 +46,16 @@ class TernaryWeightState:
         # a qweight-only checkpoint carries no latent weight (and a latent weight may come into a layer that had dropped its own)
         if prefix + "weight" in state_dict:
             if self.weight is None:  # on the layer's device, whatever device the checkpoint tensor is on
-                self.weight = nn.Parameter(torch.empty(state_dict[prefix + "weight"].shape, dtype=self.dtype, device=self.bias_a.device))
+                self.weight = nn.Parameter(torch.empty(state_dict[prefix + "weight"].shape, dtype=self.dtype, device=self._state_device()))
         elif self.weight is not None and prefix + "qweight" in state_dict:
             self.weight = None
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
         # with a latent weight, qweight is re-derived from it before the next packed forward
         self._packed = self.weight is None
+
+    def _state_device(self) -> torch.device:
+        """The device the layer's tensors live on (a re-created latent weight goes there)."""
+        return self.bias_a.device
 
     def _init_scale_a(self, x: torch.Tensor) -> None:
         # lazily initialised activation scale (2 * mean|x|, 4 * when not symmetric); the nonzero answer is remembered per version of the parameter

@@ -116,6 +116,12 @@ int ternary_linear_fused_launch(const void* x, const void* bias_a, const uint8_t
                                 int dtype, int y_f32, hipStream_t st);
 int ternary_layer_fp4_launch(const uint8_t* ximg, const uint8_t* wimg, const void* sa, const void* alpha, void* y, long M, long N, long K, int dtype,
                              hipStream_t st);
+// ternary_a8.hip
+int ta8_quantize_launch(const void* x, int8_t* q, float* r, long M, long K, long ldq, int dtype, hipStream_t st);
+bool ternary_a8_fused_ok(long M, long N, long K);
+int ternary_a8_fused_launch(const void* x, const uint8_t* q, const void* alpha, void* y, long M, long N, long K, int dtype, int raw, hipStream_t st);
+int ternary_a8_gemm_launch(const int8_t* q, const float* r, long ldq, const uint8_t* qw, const void* alpha, void* y, long M, long N, long K, int dtype,
+                           int raw, hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -852,6 +858,56 @@ int bie_ternary_linear_layer_fp4(const uint8_t* ximage, const uint8_t* wimage, c
     return ternary_layer_fp4_launch(ximage, wimage, scale_a, alpha, y, M, N, K, dtype, as_stream(stream));
 }
 
+
+// ---- ternary weights x int8 per-token activations.  Everything is checked here, before any device call.
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+static int check_ta8(const char* what, long M, long N, long K, int dtype) {
+    BIE_REQUIRE(M > 0 && M < (1L << 31) && N > 0 && N < (1L << 31) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld N=%ld (both >= 1 required)", what,
+                M, N);
+    BIE_REQUIRE(K > 0 && K % 32 == 0 && K <= 65536, BIE_ERR_INVALID_ARG, "%s: K=%ld (K %% 32 == 0 and 32 <= K <= 65536 required)", what, K);
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16, 2=f32)", what, dtype);
+    return BIE_OK;
+}
+
+int bie_ternary_a8_quantize(const void* x, int8_t* q, float* r, long M, long K, long ldq, int dtype, void* stream) {
+    int rc = check_ta8("bie_ternary_a8_quantize", M, 1, K, dtype);
+    if (rc) return rc;
+    BIE_REQUIRE(x && q && r, BIE_ERR_INVALID_ARG, "bie_ternary_a8_quantize: NULL pointer");
+    BIE_REQUIRE(ldq >= K && ldq % 16 == 0 && ldq <= (1L << 20) && M * ldq < (1L << 40), BIE_ERR_INVALID_ARG, "bie_ternary_a8_quantize: ldq=%ld (ldq >= K=%ld, ldq %% 16 == 0)",
+                ldq, K);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(q, 16) && !misaligned(r, 4), BIE_ERR_INVALID_ARG,
+                "bie_ternary_a8_quantize: x and q must be 16-byte aligned, r 4-byte aligned");
+    return ta8_quantize_launch(x, q, r, M, K, ldq, dtype, as_stream(stream));
+}
+
+int bie_ternary_a8_fused_ok(long M, long N, long K) { return ternary_a8_fused_ok(M, N, K) ? 1 : 0; }
+
+int bie_ternary_a8_linear_fused(const void* x, const uint8_t* qweight, const void* alpha, void* y, long M, long N, long K, int dtype, int raw,
+                                void* stream) {
+    int rc = check_ta8("bie_ternary_a8_linear_fused", M, N, K, dtype);
+    if (rc) return rc;
+    BIE_REQUIRE(x && qweight && y, BIE_ERR_INVALID_ARG, "bie_ternary_a8_linear_fused: NULL tensor pointer");
+    BIE_REQUIRE(!raw || !alpha, BIE_ERR_INVALID_ARG, "bie_ternary_a8_linear_fused: raw (int32 D) takes no alpha");
+    BIE_REQUIRE(ternary_a8_fused_ok(M, N, K), BIE_ERR_UNSUPPORTED, "bie_ternary_a8_linear_fused: M=%ld N=%ld K=%ld outside the one-launch range "
+                "(bie_ternary_a8_fused_ok)", M, N, K);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 4) && !misaligned(y, 4) && !misaligned(alpha, 2), BIE_ERR_INVALID_ARG,
+                "bie_ternary_a8_linear_fused: x must be 16-byte aligned, qweight and y 4-byte aligned");
+    return ternary_a8_fused_launch(x, qweight, alpha, y, M, N, K, dtype, raw ? 1 : 0, as_stream(stream));
+}
+
+int bie_ternary_a8_linear_gemm(const int8_t* q, const float* r, long ldq, const uint8_t* qweight, const void* alpha, void* y, long M, long N, long K,
+                               int dtype, int raw, void* stream) {
+    int rc = check_ta8("bie_ternary_a8_linear_gemm", M, N, K, dtype);
+    if (rc) return rc;
+    BIE_REQUIRE(q && qweight && y && (raw || r), BIE_ERR_INVALID_ARG, "bie_ternary_a8_linear_gemm: NULL tensor pointer");
+    BIE_REQUIRE(!raw || !alpha, BIE_ERR_INVALID_ARG, "bie_ternary_a8_linear_gemm: raw (int32 D) takes no alpha");
+    BIE_REQUIRE(ldq >= (K + 63) / 64 * 64 && ldq % 16 == 0 && ldq <= (1L << 20) && M * ldq < (1L << 31), BIE_ERR_INVALID_ARG,
+                "bie_ternary_a8_linear_gemm: ldq=%ld (a multiple of 16, at least K=%ld rounded up to 64)", ldq, K);
+    BIE_REQUIRE(!misaligned(q, 16) && !misaligned(r, 4) && !misaligned(qweight, 4) && !misaligned(y, 16) && !misaligned(alpha, 2), BIE_ERR_INVALID_ARG,
+                "bie_ternary_a8_linear_gemm: q and y must be 16-byte aligned, r and qweight 4-byte aligned");
+    return ternary_a8_gemm_launch(q, r, ldq, qweight, alpha, y, M, N, K, dtype, raw ? 1 : 0, as_stream(stream));
+}
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.
 int bie_ternary_conv2d_form(int B, int C, int H, int W, int OC, int ksize, int stride, int pad, int dilation) {

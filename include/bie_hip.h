@@ -535,6 +535,27 @@ int bie_ternary_conv2d_forward_fused(const void* x, const uint32_t* wlanes_mask,
 int bie_ternary_conv2d_forward_mfma(const void* x, const uint8_t* wimage, const void* scale_a, const void* alpha, void* y, int B, int C, int H, int W,
                                     int OC, int ksize, int stride, int pad, int dilation, int dtype, int y_f32, void* stream);
 
+/* ------------------------------------------------------------------------------------------ ternary a8
+ * Ternary weights x int8 per-token activations (TernaryA8LinearCuda; BitNet b1.58 "BitLinear" arithmetic; INTEGRATION.md, "Ternary
+ * W1.58A8 linear layer").  No reference implementation; these definitions are this library's own.  All activation math in fp32, no FMA,
+ * IEEE divisions:
+ *   a_m = max(max_k |x[m, k]|, 1e-5),  s_m = 127 / a_m,  q[m, k] = clamp(rint(x[m, k] * s_m), -128, 127) (int8, half to even),  r_m = a_m / 127
+ *   D[m, n] = sum_k t[n, k] * q[m, k]  (exact int32)          y[m, n] = dt( (float(D) * r_m) * alpha[n] )   (dtype 0=f16 1=bf16 2=f32)
+ *   qweight: the ternary linear's uint8 [2, N, K/8] (4-byte aligned); alpha [N] in the dtype (NULL = 1).  K % 32 == 0, K <= 65536.
+ * bie_ternary_a8_quantize: x [M, K] (16-byte aligned) -> q [M, ldq] int8 (16-byte aligned; ldq >= K, ldq % 16 == 0; bytes K .. ldq - 1 of
+ *   each row are zeroed) and r [M] fp32.
+ * bie_ternary_a8_fused_ok: 1 where the one-launch decode form is taken (small M; the bound was measured against the GEMM form).  Host only.
+ * bie_ternary_a8_linear_fused: the whole layer in one launch from x (16-byte aligned).
+ * bie_ternary_a8_linear_gemm: the same y on the matrix pipe from q / r of bie_ternary_a8_quantize with ldq >= K rounded up to 64.
+ * raw != 0: y is int32 [M, N] = D, and alpha must be NULL (r may be NULL too).  Both linear entries are bit-identical to each other, y
+ * 16-byte aligned; every argument is validated on the host before any device call. */
+int bie_ternary_a8_quantize(const void* x, int8_t* q, float* r, long M, long K, long ldq, int dtype, void* stream);
+int bie_ternary_a8_fused_ok(long M, long N, long K);
+int bie_ternary_a8_linear_fused(const void* x, const uint8_t* qweight, const void* alpha, void* y, long M, long N, long K, int dtype, int raw,
+                                void* stream);
+int bie_ternary_a8_linear_gemm(const int8_t* q, const float* r, long ldq, const uint8_t* qweight, const void* alpha, void* y, long M, long N,
+                               long K, int dtype, int raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
