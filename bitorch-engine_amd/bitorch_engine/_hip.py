@@ -114,6 +114,11 @@ SIGNATURES = {
     "bie_ternary_a8_fused_ok": (_i, [_l] * 3),
     "bie_ternary_a8_linear_fused": (_i, [_vp] * 4 + [_l] * 3 + [_i, _i, _vp]),
     "bie_ternary_a8_linear_gemm": (_i, [_vp, _vp, _l, _vp, _vp, _vp] + [_l] * 3 + [_i, _i, _vp]),
+    "bie_mxfp4_quantize": (_i, [_vp] * 3 + [_l] * 2 + [_i, _vp]),
+    "bie_mxfp4_dequant": (_i, [_vp] * 3 + [_l] * 2 + [_i, _vp]),
+    "bie_mxfp4_col_exp": (_i, [_vp] * 2 + [_l] * 2 + [_vp]),
+    "bie_mxfp4_form": (_i, [_l] * 3 + [_i]),
+    "bie_mxfp4_linear_forward": (_i, [_vp] * 6 + [_l] * 3 + [_i, _i, _vp]),
 }
 
 
@@ -126,7 +131,7 @@ TEST_HOOKS = {
 
 _HOST_ONLY = ("bie_version", "bie_last_error", "bie_mbwq_rows", "bie_mbwq_exl2_table", "bie_status_init", "bie_device_status", "bie_test_forge_reducer",
               "bie_test_forge_dependency", "bie_test_mpq_forward_plan", "bie_mpq_list_launches", "bie_mpq_list_form", "bie_mpq_prefill_form", "bie_mpq_rows_form", "bie_mpq_grouped_max_rows", "bie_mpq_list_destroy", "bie_mbwq_exl2_list_destroy",
-              "bie_ternary_conv2d_form", "bie_ternary_a8_fused_ok")
+              "bie_ternary_conv2d_form", "bie_ternary_a8_fused_ok", "bie_mxfp4_form")
 
 
 class ListEntry(ctypes.Structure):

@@ -2,3 +2,4 @@ from .mpq_layer import MPQLinearCuda, MPQLinearCudaFunction
 from .mbwq_layer import MBWQLinearCuda, MBWQLinearCudaFunction
 from .utils import unpack_qweight, pack_fp_weight, make_group_map
 from .mpq_list import MPQForwardList, MBWQExl2ForwardList
+from .mxfp4_layer import MXFP4LinearCuda, MXFP4LinearForward

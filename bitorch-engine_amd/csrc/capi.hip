@@ -122,6 +122,14 @@ bool ternary_a8_fused_ok(long M, long N, long K);
 int ternary_a8_fused_launch(const void* x, const uint8_t* q, const void* alpha, void* y, long M, long N, long K, int dtype, int raw, hipStream_t st);
 int ternary_a8_gemm_launch(const int8_t* q, const float* r, long ldq, const uint8_t* qw, const void* alpha, void* y, long M, long N, long K, int dtype,
                            int raw, hipStream_t st);
+// mxfp4.hip
+int mxfp4_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st);
+int mxfp4_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, long K, int dtype, hipStream_t st);
+int mxfp4_col_exp_launch(const uint8_t* sc, uint8_t* ecol, long N, long K, hipStream_t st);
+int mxfp4_form(long M, long N, long K, int dtype);
+bool mxfp4_decode_ok(long M);
+int mxfp4_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
+                         int dtype, int form, hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -907,6 +915,56 @@ int bie_ternary_a8_linear_gemm(const int8_t* q, const float* r, long ldq, const 
     BIE_REQUIRE(!misaligned(q, 16) && !misaligned(r, 4) && !misaligned(qweight, 4) && !misaligned(y, 16) && !misaligned(alpha, 2), BIE_ERR_INVALID_ARG,
                 "bie_ternary_a8_linear_gemm: q and y must be 16-byte aligned, r and qweight 4-byte aligned");
     return ternary_a8_gemm_launch(q, r, ldq, qweight, alpha, y, M, N, K, dtype, raw ? 1 : 0, as_stream(stream));
+}
+
+// ---- MXFP4 weights.  Everything is checked here, before any device call.
+static int check_mx(const char* what, long N, long K) {
+    BIE_REQUIRE(N > 0 && N < (1L << 31), BIE_ERR_INVALID_ARG, "%s: N=%ld (N >= 1 required)", what, N);
+    BIE_REQUIRE(K >= 32 && K % 32 == 0 && K <= (1L << 20) && N * K < (1L << 40), BIE_ERR_INVALID_ARG, "%s: K=%ld (K %% 32 == 0 and 32 <= K <= 2^20 required)",
+                what, K);
+    return BIE_OK;
+}
+
+int bie_mxfp4_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream) {
+    int rc = check_mx("bie_mxfp4_quantize", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_mxfp4_quantize: dtype %d (0=f16, 1=bf16, 2=f32)", dtype);
+    BIE_REQUIRE(w && qweight && scales, BIE_ERR_INVALID_ARG, "bie_mxfp4_quantize: NULL pointer");
+    BIE_REQUIRE(!misaligned(w, 4) && !misaligned(qweight, 16), BIE_ERR_INVALID_ARG, "bie_mxfp4_quantize: w must be 4-byte aligned, qweight 16-byte aligned");
+    return mxfp4_quantize_launch(w, qweight, scales, N, K, dtype, as_stream(stream));
+}
+
+int bie_mxfp4_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long N, long K, int dtype, void* stream) {
+    int rc = check_mx("bie_mxfp4_dequant", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_mxfp4_dequant: dtype %d (0=f16, 1=bf16, 2=f32)", dtype);
+    BIE_REQUIRE(w && qweight && scales, BIE_ERR_INVALID_ARG, "bie_mxfp4_dequant: NULL pointer");
+    BIE_REQUIRE(!misaligned(w, 4) && !misaligned(qweight, 16), BIE_ERR_INVALID_ARG, "bie_mxfp4_dequant: w must be 4-byte aligned, qweight 16-byte aligned");
+    return mxfp4_dequant_launch(qweight, scales, w, N, K, dtype, as_stream(stream));
+}
+
+int bie_mxfp4_col_exp(const uint8_t* scales, uint8_t* e_col, long N, long K, void* stream) {
+    int rc = check_mx("bie_mxfp4_col_exp", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(scales && e_col, BIE_ERR_INVALID_ARG, "bie_mxfp4_col_exp: NULL pointer");
+    return mxfp4_col_exp_launch(scales, e_col, N, K, as_stream(stream));
+}
+
+int bie_mxfp4_form(long M, long N, long K, int dtype) { return mxfp4_form(M, N, K, dtype); }
+
+int bie_mxfp4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                             long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mx("bie_mxfp4_linear_forward", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: M=%ld (M >= 1 required)", M);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "bie_mxfp4_linear_forward: dtype %d (0=f16, 1=bf16)", dtype);
+    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: form %d (-1 = plan, 0 = decode, 1 = prefill)", form);
+    if (form < 0) form = mxfp4_form(M, N, K, dtype);
+    BIE_REQUIRE(form == 1 || mxfp4_decode_ok(M), BIE_ERR_UNSUPPORTED, "bie_mxfp4_linear_forward: the decode form takes M <= 16 (M=%ld)", M);
+    BIE_REQUIRE(x && qweight && scales && y && (form == 0 || e_col), BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: NULL tensor pointer (the prefill form needs e_col)");
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(y, 2) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mxfp4_linear_forward: x and qweight must be 16-byte aligned, y and bias 2-byte aligned");
+    return mxfp4_forward_launch(x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
 }
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.

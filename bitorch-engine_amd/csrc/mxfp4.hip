@@ -1,0 +1,417 @@
+// MXFP4 (OCP microscaling FP4) weight-only linear layer for gfx950: y = x . W^T (+ bias), x fp16 / bf16.  No reference implementation
+// exists; the format and the arithmetic are this library's own (include/bie_hip.h, INTEGRATION.md "MXFP4 linear layer").
+//
+//   qweight uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j + 1 in the high nibble (the `blocks` of gpt-oss-style checkpoints)
+//   scales  uint8 [N, K/32]: E8M0, code s = 2^(s - 127) for s in 0..254, 255 = NaN
+//   W[n, k] = e2m1(code) * 2^(s - 127), e2m1 = sign bit 3, magnitude {0, 0.5, 1, 1.5, 2, 3, 4, 6}[code & 7]   (exact in fp32)
+//   y[m, n] = dt( sum_k x[m, k] * W[n, k] + bias[n] ), products exact, the sum in fp32, one rounding to the dtype
+//
+// Decode form (mx_decode_kernel, M <= 16): one launch, a workgroup per C output columns, its 256 threads striding K by 16 values
+// (8 bytes of codes and the half-block's scale byte per column, non-temporal loads).  v_cvt_scalef32_pk_{bf16,f16}_fp4 turns two codes
+// into two exact 16-bit values (scale 1.0), v_dot2_f32_{bf16,f16} sums 16 products per row into fp32, and that partial is multiplied by
+// the block's fp32 scale (a power of two: exact).  No 16-bit image of W exists, so the fp16 form has the fp32 range of W.  The K-split
+// partials are summed on the DPP network, then across the 4 waves in LDS.
+// Prefill form (mx_gemm_kernel): a 128 x 128 tile GEMM on v_mfma_f32_32x32x16_{bf16,f16}, double-buffered LDS.  The weight tile is
+// staged PACKED (32 bytes per row and 64-k stage, plus two scale words) and converted to B fragments after the LDS read: a lane's 8-k
+// fragment is 4 code bytes = 4 converts.  Each column is rebiased by its largest scale code e_col[n] (bie_mxfp4_col_exp, computed once
+// at load time): fragments hold e2m1 * 2^(s - e_col[n]) <= 6 and the fp32 epilogue multiplies by 2^(e_col[n] - 127).  A column with a
+// scale-255 block has e_col = 255, which makes the whole column NaN in the epilogue.
+#include "mfma_pipe.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+typedef __bf16 mx_bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 mx_half8_t __attribute__((ext_vector_type(8)));
+
+// E8M0 -> fp32: 2^(s - 127), code 0 the subnormal 2^-127 (not 0.0), code 255 NaN (not +inf, which the plain s << 23 would give)
+__device__ __forceinline__ float e8m0_f32(uint32_t s) { return __uint_as_float(s == 0u ? 0x00400000u : s == 255u ? 0x7fc00000u : s << 23); }
+
+// 2^d for d <= 0 as the convert's scale: 0 below 2^-126 (e2m1 * 2^d then lies below every fp16 / bf16 normal the fragments keep)
+__device__ __forceinline__ float mx_rebias(uint32_t s, uint32_t e) {
+    const int d = (int)s - (int)e;
+    return __uint_as_float(d < -126 ? 0u : (uint32_t)(d + 127) << 23);
+}
+
+__device__ __forceinline__ float mx_e2m1(uint32_t c) {  // the code's value as fp32 bits: 0, 0.5, then (1 + m / 2) * 2^(e - 1)
+    const uint32_t i = c & 7u;
+    const uint32_t mag = i < 2u ? (i ? 0x3f000000u : 0u) : ((126u + (i >> 1)) << 23) | ((i & 1u) << 22);
+    return __uint_as_float(mag | ((c & 8u) << 28));
+}
+
+// ---- quantise / dequant / column exponent ---------------------------------------------------------------------------------------------
+template <int DT>
+__device__ __forceinline__ float mx_load(const void* p, long i) { return dt_traits<DT>::load(p, i); }
+
+// |a| -> E2M1 magnitude index, round to nearest, ties to the even index (0.25 -> 0, 0.75 -> 2, 1.25 -> 2, 1.75 -> 4, 2.5 -> 4, 3.5 -> 6,
+// 5 -> 6), saturating at 6
+__device__ __forceinline__ uint32_t mx_round_e2m1(float a) {
+    return a <= 0.25f ? 0u : a < 0.75f ? 1u : a <= 1.25f ? 2u : a < 1.75f ? 3u : a <= 2.5f ? 4u : a < 3.5f ? 5u : a <= 5.0f ? 6u : 7u;
+}
+
+// One thread per 32-value block: amax, e = floor(log2 amax) - 2 clamped to [-127, 127] (from the fp32 exponent bits, subnormal amax by
+// its leading bit), codes of w * 2^-e (exact: a power-of-two multiply of a normal result).  An all-zero block: scale 0, codes 0.
+template <int DT>
+__global__ __launch_bounds__(256) void mx_quantize_kernel(const void* __restrict__ w, uint8_t* __restrict__ qw, uint8_t* __restrict__ sc, long nblk) {
+    const long b = (long)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblk) return;
+    float v[32];
+    float amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 32; i++) {
+        v[i] = mx_load<DT>(w, b * 32 + i);
+        amax = fmaxf(amax, fabsf(v[i]));
+    }
+    uint4_t codes = {0u, 0u, 0u, 0u};
+    uint32_t scode = 0u;
+    if (amax > 0.0f) {
+        const uint32_t bits = __float_as_uint(amax);
+        const int ex = (int)(bits >> 23);
+        const int fl = ex ? ex - 127 : (31 - __builtin_clz(bits & 0x7fffffu)) - 149;  // floor(log2(amax))
+        const int e = min(max(fl - 2, -127), 127);
+        scode = (uint32_t)(e + 127);
+        const float inv = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e, normal: e <= 125 for any finite amax
+#pragma unroll
+        for (int i = 0; i < 32; i++) {
+            const uint32_t c = mx_round_e2m1(fabsf(v[i] * inv)) | ((__float_as_uint(v[i]) >> 28) & 8u);
+            codes[i >> 3] |= c << (4 * (i & 7));
+        }
+    }
+    reinterpret_cast<uint4_t*>(qw)[b] = codes;
+    sc[b] = (uint8_t)scode;
+}
+
+// One thread per 32-value block: W in fp32 (exact), rounded once to the output dtype
+template <int DT>
+__global__ __launch_bounds__(256) void mx_dequant_kernel(const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, void* __restrict__ w, long nblk) {
+    const long b = (long)blockIdx.x * 256 + threadIdx.x;
+    if (b >= nblk) return;
+    const uint4_t codes = reinterpret_cast<const uint4_t*>(qw)[b];
+    const float s = e8m0_f32(sc[b]);
+#pragma unroll
+    for (int i = 0; i < 32; i++) dt_traits<DT>::store(w, b * 32 + i, mx_e2m1(codes[i >> 3] >> (4 * (i & 7))) * s);
+}
+
+// e_col[n] = 255 if row n has a scale-255 block, else the largest scale code of the row.  One wave per row: the lanes read the row's
+// scale bytes side by side, the maximum is taken across the wave.
+__global__ __launch_bounds__(256) void mx_col_exp_kernel(const uint8_t* __restrict__ sc, uint8_t* __restrict__ ecol, int N, int KB) {
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= N) return;  // wave-uniform
+    uint32_t e = 0u;
+    for (int i = lane; i < KB; i += 64) e = max(e, (uint32_t)sc[(long)n * KB + i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) e = max(e, (uint32_t)__shfl_xor((int)e, o, 64));
+    if (lane == 0) ecol[n] = (uint8_t)e;
+}
+
+// ---- decode form --------------------------------------------------------------------------------------------------------------------
+template <int DT> struct mx_pair;
+template <> struct mx_pair<BIE_BF16> {
+    typedef bf16x2_t t;
+    template <int SEL>
+    static __device__ __forceinline__ t cvt(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, SEL); }
+    static __device__ __forceinline__ float dot(t a, uint32_t b, float c) { return __builtin_amdgcn_fdot2_f32_bf16(a, __builtin_bit_cast(t, b), c, false); }
+};
+template <> struct mx_pair<BIE_F16> {
+    typedef half2_t t;
+    template <int SEL>
+    static __device__ __forceinline__ t cvt(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, SEL); }
+    static __device__ __forceinline__ float dot(t a, uint32_t b, float c) { return __builtin_amdgcn_fdot2(a, __builtin_bit_cast(t, b), c, false); }
+};
+
+template <int CTRL, int RMASK>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RMASK, 0xf, false));
+}
+__device__ __forceinline__ float wave_sum_f32(float v) {  // wave_sum_dpp's network (bie_common.h) on fp32; the total of lane 63
+    v = dpp_add<0xB1, 0xf>(v);
+    v = dpp_add<0x4E, 0xf>(v);
+    v = dpp_add<0x141, 0xf>(v);
+    v = dpp_add<0x140, 0xf>(v);
+    v = dpp_add<0x142, 0xa>(v);
+    v = dpp_add<0x143, 0xc>(v);
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// Workgroup: columns C * blockIdx.x .. + C - 1 (clamped reads past N, never stored), rows 0 .. M - 1 (M <= R).  Thread t takes the
+// 16-value units u = t, t + 256, ... of K: per column 8 code bytes and the scale byte of block u / 2.
+template <int DT, int R, int C>
+__global__ __launch_bounds__(256) void mx_decode_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                        const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
+    typedef mx_pair<DT> P;
+    __shared__ float red[4][C][R];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int U = K >> 4, KB = K >> 5;
+    const int n0 = blockIdx.x * C;
+    const uint8_t* wrow[C];
+    const uint8_t* srow[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const long n = min(n0 + c, N - 1);
+        wrow[c] = qw + n * (K >> 1);
+        srow[c] = sc + n * KB;
+    }
+    float acc[C][R];
+#pragma unroll
+    for (int c = 0; c < C; c++)
+#pragma unroll
+        for (int r = 0; r < R; r++) acc[c][r] = 0.0f;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint2_t wb[C];
+        uint32_t sb[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            wb[c] = __builtin_nontemporal_load(reinterpret_cast<const uint2_t*>(wrow[c]) + u);
+            sb[c] = __builtin_nontemporal_load(srow[c] + (u >> 1));
+        }
+        typename P::t wv[C][8];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            wv[c][0] = P::template cvt<0>(wb[c].x); wv[c][1] = P::template cvt<1>(wb[c].x);
+            wv[c][2] = P::template cvt<2>(wb[c].x); wv[c][3] = P::template cvt<3>(wb[c].x);
+            wv[c][4] = P::template cvt<0>(wb[c].y); wv[c][5] = P::template cvt<1>(wb[c].y);
+            wv[c][6] = P::template cvt<2>(wb[c].y); wv[c][7] = P::template cvt<3>(wb[c].y);
+        }
+        float s[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) s[c] = e8m0_f32(sb[c]);
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (r < M) {  // M is uniform
+                const uint4_t* xp = reinterpret_cast<const uint4_t*>(x + (long)r * K) + 2 * u;
+                const uint4_t x0 = xp[0], x1 = xp[1];
+                const uint32_t xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    float p = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) p = P::dot(wv[c][j], xv[j], p);
+                    acc[c][r] += p * s[c];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++)
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (r < M) {
+                const float v = wave_sum_f32(acc[c][r]);
+                if (lane == 0) red[wave][c][r] = v;
+            }
+        }
+    __syncthreads();
+    if (threadIdx.x < C * R) {
+        const int c = threadIdx.x / R, r = threadIdx.x % R, n = n0 + c;
+        if (n < N && r < M) {
+            float v = ((red[0][c][r] + red[1][c][r]) + red[2][c][r]) + red[3][c][r];
+            if (bias) v += dt_traits<DT>::load(bias, n);
+            dt_traits<DT>::store(y, (long)r * N + n, v);
+        }
+    }
+}
+
+// ---- prefill form -------------------------------------------------------------------------------------------------------------------
+constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 64;
+constexpr int MX_APITCH = MX_BK * 2 + 16;  // bytes per x row in LDS (16-byte pad: the fragment reads of 32 rows spread over the banks)
+constexpr int MX_BPITCH = 36;              // bytes per weight row: 32 code bytes + 4 (9 dwords, the 32 rows of a read on distinct banks)
+constexpr int MX_STAGE = MX_BM * MX_APITCH + MX_BN * MX_BPITCH + MX_BN * 2 * 4;  // x, codes, the two fp32 rebiased scales per row
+
+template <int DT> struct mx_frag;
+template <> struct mx_frag<BIE_BF16> {
+    typedef mx_bf16x8_t t;
+    static __device__ __forceinline__ t cvt(uint32_t w, float s) {
+        const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 1);
+        const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 3);
+        return t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+    }
+    static __device__ __forceinline__ float16_t mfma(const t& a, const t& b, const float16_t& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct mx_frag<BIE_F16> {
+    typedef mx_half8_t t;
+    static __device__ __forceinline__ t cvt(uint32_t w, float s) {
+        const half2_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 1);
+        const half2_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 3);
+        return t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+    }
+    static __device__ __forceinline__ float16_t mfma(const t& a, const t& b, const float16_t& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+// 4 waves as 2 x 2, wave tile 64 x 64 (2 x 2 MFMA tiles).  Per 64-k stage a thread loads 4 x 16 bytes of x, 16 code bytes and one
+// scale byte into registers while the MFMAs run on the other LDS buffer, then writes them (the scale already rebiased to fp32).
+// Past M / N / K: x and codes load as zero, scales as 1.0, so the padding adds exact zeros.
+template <int DT>
+__global__ __launch_bounds__(256) void mx_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                      const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int M, int N,
+                                                      int K, int tiles_n) {
+    typedef mx_frag<DT> F;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX_STAGE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    int tile_m, tile_n;
+    pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
+    const int m0 = tile_m * MX_BM, n0 = tile_n * MX_BN;
+    const int KT = (K + MX_BK - 1) / MX_BK, KB = K >> 5;
+
+    // this thread's load slots
+    const int bn = t >> 1, bh = t & 1;  // weight row bn of the tile, 16-byte half bh; scale block bh of the stage
+    const int nb = n0 + bn;
+    const bool nb_ok = nb < N;
+    const uint8_t* wsrc = qw + (long)min(nb, N - 1) * (K >> 1) + bh * 16;
+    const uint8_t* ssrc = sc + (long)min(nb, N - 1) * KB + bh;
+    const uint32_t e = nb_ok ? ecol[nb] : 0u;
+    uint4_t ra[4], rb;
+    float rs;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7, m = m0 + row, k = kt * MX_BK + c16 * 8;
+            ra[i] = (m < M && k < K) ? *reinterpret_cast<const uint4_t*>(x + (long)m * K + k) : uint4_t{0u, 0u, 0u, 0u};
+        }
+        const bool kin = kt * MX_BK + bh * 32 < K;
+        rb = (nb_ok && kin) ? __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wsrc + kt * 32)) : uint4_t{0u, 0u, 0u, 0u};
+        rs = (nb_ok && kin) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), e) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MX_APITCH + c16 * 16) = ra[i];
+        }
+        uint32_t* wb = reinterpret_cast<uint32_t*>(st + MX_BM * MX_APITCH + bn * MX_BPITCH + bh * 16);
+        wb[0] = rb.x; wb[1] = rb.y; wb[2] = rb.z; wb[3] = rb.w;
+        reinterpret_cast<float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH)[bn * 2 + bh] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * MX_STAGE;
+        const float* ss = reinterpret_cast<const float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH);
+#pragma unroll
+        for (int ks = 0; ks < MX_BK / 16; ks++) {
+            typename F::t a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX_APITCH + ks * 32 + hh * 16));
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int n = wx * 64 + j * 32 + rl;
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(st + MX_BM * MX_APITCH + n * MX_BPITCH + ks * 8 + hh * 4);
+                b[j] = F::cvt(w, ss[n * 2 + (ks >> 1)]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: column n = lane & 31, row m = (r & 3) + 8 (r >> 2) + 4 hh
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int n = n0 + wx * 64 + j * 32 + rl;
+        if (n >= N) continue;
+        const float cs = e8m0_f32(ecol[n]);
+        const float bv = bias ? dt_traits<DT>::load(bias, n) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int m = m0 + wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (m < M) {
+                    float v = acc[i][j][r] * cs;
+                    if (bias) v += bv;
+                    dt_traits<DT>::store(y, (long)m * N + n, v);
+                }
+            }
+    }
+}
+
+// ---- plan and launchers -----------------------------------------------------------------------------------------------------------------
+// The decode form serves M <= MX_DECODE_ROWS (instances R = 1, 2, 4, 8, 16 rows); larger M takes the MFMA GEMM.  The bound of the plan
+// was measured (tools/mxfp4_bench.py, profiles/mxfp4_bench.jsonl, the M sweep): the decode form was ahead at every M <= 16 on
+// 4096 x 4096, 4096 -> 11008 and 11008 -> 4096 in fp16 and bf16 (at M = 16: 20.1 / 52.6 / 36.7 us against 84.9 / 91.6 / 241.0), the
+// GEMM having only ceil(N / 128) workgroups at such M.
+constexpr int MX_DECODE_ROWS = 16;
+constexpr int MX_PLAN_ROWS = 16;
+
+int mxfp4_form(long M, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_FORM", -1);
+    if (f == 0 && M <= MX_DECODE_ROWS) return 0;
+    if (f == 1) return 1;
+    return M <= MX_PLAN_ROWS ? 0 : 1;
+}
+
+bool mxfp4_decode_ok(long M) { return M >= 1 && M <= MX_DECODE_ROWS; }
+
+int mxfp4_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st) {
+    const long nblk = N * (K / 32);
+    const dim3 grid((unsigned)cdivl(nblk, 256));
+    if (dtype == BIE_F16) hipLaunchKernelGGL(mx_quantize_kernel<BIE_F16>, grid, dim3(256), 0, st, w, qw, sc, nblk);
+    else if (dtype == BIE_BF16) hipLaunchKernelGGL(mx_quantize_kernel<BIE_BF16>, grid, dim3(256), 0, st, w, qw, sc, nblk);
+    else hipLaunchKernelGGL(mx_quantize_kernel<BIE_F32>, grid, dim3(256), 0, st, w, qw, sc, nblk);
+    return check_launch("mx_quantize_kernel");
+}
+
+int mxfp4_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, long K, int dtype, hipStream_t st) {
+    const long nblk = N * (K / 32);
+    const dim3 grid((unsigned)cdivl(nblk, 256));
+    if (dtype == BIE_F16) hipLaunchKernelGGL(mx_dequant_kernel<BIE_F16>, grid, dim3(256), 0, st, qw, sc, w, nblk);
+    else if (dtype == BIE_BF16) hipLaunchKernelGGL(mx_dequant_kernel<BIE_BF16>, grid, dim3(256), 0, st, qw, sc, w, nblk);
+    else hipLaunchKernelGGL(mx_dequant_kernel<BIE_F32>, grid, dim3(256), 0, st, qw, sc, w, nblk);
+    return check_launch("mx_dequant_kernel");
+}
+
+int mxfp4_col_exp_launch(const uint8_t* sc, uint8_t* ecol, long N, long K, hipStream_t st) {
+    hipLaunchKernelGGL(mx_col_exp_kernel, dim3((unsigned)cdivl(N, 4)), dim3(256), 0, st, sc, ecol, (int)N, (int)(K / 32));
+    return check_launch("mx_col_exp_kernel");
+}
+
+template <int DT, int R>
+static void mx_decode_launch_r(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    constexpr int C = R >= 4 ? 8 : 4;  // columns per workgroup: x is read once per C columns
+    hipLaunchKernelGGL((mx_decode_kernel<DT, R, C>), dim3((unsigned)cdiv(N, C)), dim3(256), 0, st, x, qw, sc, bias, y, M, N, K);
+}
+
+template <int DT>
+static void mx_decode_launch_dt(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    if (M <= 1) mx_decode_launch_r<DT, 1>(x, qw, sc, bias, y, M, N, K, st);
+    else if (M <= 2) mx_decode_launch_r<DT, 2>(x, qw, sc, bias, y, M, N, K, st);
+    else if (M <= 4) mx_decode_launch_r<DT, 4>(x, qw, sc, bias, y, M, N, K, st);
+    else if (M <= 8) mx_decode_launch_r<DT, 8>(x, qw, sc, bias, y, M, N, K, st);
+    else mx_decode_launch_r<DT, 16>(x, qw, sc, bias, y, M, N, K, st);
+}
+
+int mxfp4_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
+                         int dtype, int form, hipStream_t st) {
+    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
+    if (form == 0) {
+        if (dtype == BIE_F16) mx_decode_launch_dt<BIE_F16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
+        else mx_decode_launch_dt<BIE_BF16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
+        return check_launch("mx_decode_kernel");
+    }
+    const int tn = (int)cdivl(N, MX_BN);
+    const dim3 grid((unsigned)(cdivl(M, MX_BM) * tn));
+    if (dtype == BIE_F16) hipLaunchKernelGGL(mx_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
+    else hipLaunchKernelGGL(mx_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
+    return check_launch("mx_gemm_kernel");
+}
+
+}  // namespace bie

@@ -556,6 +556,32 @@ int bie_ternary_a8_linear_fused(const void* x, const uint8_t* qweight, const voi
 int bie_ternary_a8_linear_gemm(const int8_t* q, const float* r, long ldq, const uint8_t* qweight, const void* alpha, void* y, long M, long N,
                                long K, int dtype, int raw, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4
+ * MXFP4 (OCP microscaling FP4) weights x fp16 / bf16 activations (MXFP4LinearCuda; INTEGRATION.md, "MXFP4 linear layer").  No reference
+ * implementation; these definitions are this library's own.
+ *   qweight  uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j + 1 in the high nibble (16-byte aligned)
+ *   scales   uint8 [N, K/32]: E8M0, code s = 2^(s - 127) for s in 0..254, 255 = NaN
+ *   W[n, k]  = e2m1(code) * 2^(s - 127), e2m1 = sign bit 3, magnitude {0, 0.5, 1, 1.5, 2, 3, 4, 6}[code & 7]   (exact in fp32)
+ *   y[m, n]  = dt( sum_k x[m, k] * W[n, k] + bias[n] ): products exact, sums in fp32, one rounding to the dtype (0=f16 1=bf16)
+ *   K % 32 == 0, 32 <= K <= 2^20; any N >= 1.
+ * bie_mxfp4_quantize: w [N, K] (dtype 0/1/2, 4-byte aligned) -> qweight / scales by the OCP MX v1.0 rule: per block of 32, in fp32,
+ *   e = floor(log2 amax) - 2 clamped to [-127, 127], codes = w / 2^e rounded to nearest E2M1 (ties to even, saturating at 6, the sign
+ *   bit follows w); an all-zero block gets scale 0 and zero codes.
+ * bie_mxfp4_dequant: -> W [N, K] in dtype 0/1/2 (computed in fp32, rounded once; fp16 overflows to inf beyond 65504).
+ * bie_mxfp4_col_exp: e_col [N] uint8 = the largest scale code of row n, 255 where the row has a NaN block.  Needed by the prefill form.
+ * bie_mxfp4_form: 0 = decode form (M <= 16), 1 = prefill form (MFMA GEMM).  The plan takes the decode form for M <= 16 (measured); BIE_MXFP4_FORM=0/1
+ *   forces a form (0 only where M <= 16).  Host only.
+ * bie_mxfp4_linear_forward: x [M, K] (16-byte aligned), bias [N] in the dtype or NULL, y [M, N]; e_col of bie_mxfp4_col_exp (the
+ *   prefill form reads it; the decode form takes NULL); form -1 = bie_mxfp4_form.  The decode form keeps the fp32 range of W; the prefill
+ *   form flushes weights more than 2^24 (fp16) / 2^126 (bf16) below their column's largest scale to zero.  Every argument is validated on
+ *   the host before any device call; nothing synchronises with the host. */
+int bie_mxfp4_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream);
+int bie_mxfp4_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long N, long K, int dtype, void* stream);
+int bie_mxfp4_col_exp(const uint8_t* scales, uint8_t* e_col, long N, long K, void* stream);
+int bie_mxfp4_form(long M, long N, long K, int dtype);
+int bie_mxfp4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                             long N, long K, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
