@@ -2,6 +2,7 @@
 // the semantics are this library's own (include/bie_hip.h, INTEGRATION.md "Ternary W1.58A8 linear layer").
 //
 //   a_m = max(max_k |x[m, k]|, 1e-5),  s_m = 127 / a_m,  q[m, k] = clamp(rint(x[m, k] * s_m), -128, 127),  r_m = a_m / 127   (fp32, no FMA)
+//   (a_m = NaN where row m holds a NaN or an infinity: every y of that row is NaN)
 //   D[m, n] = sum_k t[n, k] * q[m, k]  (exact int32; K <= 65536)          y[m, n] = dt((float(D) * r_m) * alpha[n])
 //
 // The weights are ternary.hip's qweight, uint8 [2, N, K/8] (plane 0 = non-zero mask, plane 1 = +1), read as packed bits by both forms:
@@ -52,20 +53,21 @@ __device__ __forceinline__ int ta8_q(float v, float s) {  // clamp(rint(v * s), 
     return (int)fminf(fmaxf(__builtin_rintf(v * s), -128.0f), 127.0f);
 }
 
-__device__ __forceinline__ float wave_max(float v) {
+__device__ __forceinline__ uint32_t wave_umax(uint32_t v) {
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
     return v;
 }
 
 // absmax of R rows of x (rows >= M contribute nothing), reduced over the 256 threads: every thread returns the same a_m.  Its static LDS (128 bytes at most) is why the decode
-// form keeps 1 KiB of the 64 KiB free
+// form keeps 1 KiB of the 64 KiB free.  The max is taken on the bits of |x|, which order as the values do and put every NaN above +inf, so a
+// row holding a NaN or an infinity gets a_m = NaN (fmaxf would drop a NaN): r_m is NaN and so is every y of that row, in both forms.
 template <int DT, int R>
 __device__ __forceinline__ void ta8_absmax(const void* x, int M, int K, float (&a)[R]) {
-    __shared__ float red[4][R];
-    float mx[R];
+    __shared__ uint32_t red[4][R];
+    uint32_t mx[R];
 #pragma unroll
-    for (int r = 0; r < R; r++) mx[r] = 0.0f;
+    for (int r = 0; r < R; r++) mx[r] = 0u;
     for (int t = threadIdx.x; t < (K >> 3); t += 256) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -73,19 +75,22 @@ __device__ __forceinline__ void ta8_absmax(const void* x, int M, int K, float (&
                 float v[8];
                 ta8_load8<DT>(x, (long)r * K + t * 8, v);
 #pragma unroll
-                for (int e = 0; e < 8; e++) mx[r] = fmaxf(mx[r], fabsf(v[e]));
+                for (int e = 0; e < 8; e++) mx[r] = max(mx[r], __float_as_uint(v[e]) & 0x7fffffffu);
             }
         }
     }
     const int wave = threadIdx.x >> 6;
 #pragma unroll
     for (int r = 0; r < R; r++) {
-        const float w = wave_max(mx[r]);
+        const uint32_t w = wave_umax(mx[r]);
         if ((threadIdx.x & 63) == 0) red[wave][r] = w;
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < R; r++) a[r] = fmaxf(fmaxf(fmaxf(red[0][r], red[1][r]), fmaxf(red[2][r], red[3][r])), 1e-5f);
+    for (int r = 0; r < R; r++) {
+        const uint32_t m = max(max(red[0][r], red[1][r]), max(red[2][r], red[3][r]));
+        a[r] = m >= 0x7f800000u ? __uint_as_float(0x7fc00000u) : fmaxf(__uint_as_float(m), 1e-5f);
+    }
 }
 
 // One workgroup per row: q [M, ldq] int8 (bytes K .. ldq - 1 zeroed), r [M] fp32.

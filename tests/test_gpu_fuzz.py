@@ -1,7 +1,10 @@
 """Randomised shape sweeps (run with -m gpu on an MI355X): the tests/sweeps/fuzz_*.py generators at a size that takes seconds -- random bit widths, group
 sizes, ragged N, every dispatch boundary of M, random mixed-bit band structures, random layer lists -- each configuration against the CPU
 restatement.  A configuration the library REFUSES (RuntimeError with its message) is acceptable; a wrong value, a NaN or a crash is not.
-The long runs (2000 / 800 / 600 cases, no finding) are recorded in profiles/r05_fuzz.txt."""
+The long runs (2000 / 800 / 600 cases, no finding) are recorded in profiles/r05_fuzz.txt.  The ternary linear, ternary conv2d, ternary
+W1.58A8 and MXFP4 slices (tests/sweeps/fuzz_ternary_mx.py: every form of each op, decode grids wider than one column sweep, K at the LDS
+bounds, sign and scale edges) have their long run in profiles/fuzz_ternary_mx.txt; TERNARY_MX_SLICES is also read by the CPU test that
+checks, without a GPU, that these seeds draw every form."""
 import os
 import sys
 
@@ -58,3 +61,21 @@ def test_random_call_programs_never_get_another_tensors_result_from_the_sibling_
     r = fuzz_sibling_groups.run(parents=30, seed=seed)
     assert not r["bad"], r["bad"][:2]
     assert r["calls"] > 500 and r["grouped_launches"] > 0 and r["served_from_group"] > 0, r
+
+
+# op -> (cases, seed): tests/test_ternary_mx_boundaries_cpu.py checks on the host that these draws reach every form of each op
+TERNARY_MX_SLICES = {"tern": (200, 601), "tconv": (150, 602), "ta8": (200, 603), "mx": (200, 604)}
+
+
+@pytest.mark.parametrize("op", sorted(TERNARY_MX_SLICES))
+def test_randomised_ternary_and_mxfp4_forms_against_the_references(op):
+    """tests/sweeps/fuzz_ternary_mx.py: random shapes, dtypes and inputs of one op on every form that accepts them, against the
+    high-precision references of the fixed-shape tests.  Every form of the op is reached; tern and ta8 reach a decode grid with N > 16384."""
+    import fuzz_ternary_mx
+    cases, seed = TERNARY_MX_SLICES[op]
+    r = fuzz_ternary_mx.run(cases=cases, seed=seed, ops=(op,))["ops"][op]
+    assert not r["bad"], r["bad"][:3]
+    assert r["ok"] >= cases - 3, r
+    assert all(n > 0 for n in r["forms"].values()), r["forms"]
+    if op in ("tern", "ta8"):
+        assert r["forms"]["decode_wide"] > 0, r["forms"]
