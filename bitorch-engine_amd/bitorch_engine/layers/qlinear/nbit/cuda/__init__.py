@@ -3,3 +3,4 @@ from .mbwq_layer import MBWQLinearCuda, MBWQLinearCudaFunction
 from .utils import unpack_qweight, pack_fp_weight, make_group_map
 from .mpq_list import MPQForwardList, MBWQExl2ForwardList
 from .mxfp4_layer import MXFP4LinearCuda, MXFP4LinearForward
+from .mxfp4_a4_layer import MXFP4A4LinearCuda, MXFP4A4LinearForward

@@ -1,0 +1,409 @@
+// MXFP4 W4A4 linear layer for gfx950: the MXFP4 weights of mxfp4.hip against activations quantised to MXFP4 on the fly, contracted on the
+// block-scaled matrix instructions with REAL block scales (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A4 linear layer").
+//
+//   xq uint8 [M, K/2], xs uint8 [M, K/32]: x quantised per row and block of 32 by the OCP MX v1.0 rule of mx_quantize_kernel (mxfp4.hip)
+//   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (its codes are unspecified), else 0
+//   y[m, n] = dt( sum_b 2^(xs[m, b] + scales[n, b] - 254) * (sum_{k in b} e2m1(xq) * e2m1(qweight)) + bias[n] )
+//   y[m, :] = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255 (a weight block with scale code 255)
+//
+// How the instructions read their scale operands was pinned on the card by tools/probe/probe_mx_scale.hip
+// (profiles/mxfp4_a4_scale_probe.txt): in v_mfma_scale_f32_32x32x64_f8f6f4 lane l holds the 32 values of row (column) l & 31, k-block
+// l >> 5, and its OWN scale byte applies to exactly those 32 values; in v_mfma_scale_f32_16x16x128_f8f6f4 row l & 15, k-block l >> 4.
+// A lane's operand is therefore 16 contiguous bytes of qweight [N, K/2] (or xq) and its scale the matching byte of scales [N, K/32]:
+// nothing is converted or re-arranged.  The kernels keep the lane's scale in byte 0 of the scale register (byte select 0).
+//
+// Quantise kernel (mxa4_quantize_kernel): a workgroup per row of x, a block of 32 per 4 lanes (16-byte loads, one dword of codes per
+// lane), the block maximum over the 4 lanes on the DPP network, the row's non-finite flag through the workgroup's barrier.
+// Decode form (mxa4_decode_kernel, M <= 64): a workgroup per 16 output columns, K split over its 4 waves; every wave loads its B
+// fragments straight from qweight (non-temporal, 16 bytes per lane) and the x fragments from xq (cache-resident), one
+// 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS.
+// Prefill form (mxa4_gemm_kernel): a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2, packed codes and scale bytes staged
+// through registers into double-buffered LDS (128 k per stage); per 64 k a wave reads WM + WN fragments and as many scale bytes and
+// issues WM * WN MFMAs.  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one row of y.
+#include "mfma_pipe.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+namespace {
+
+typedef int mxa4_v8i __attribute__((ext_vector_type(8)));
+typedef float mxa4_v4f __attribute__((ext_vector_type(4)));
+
+// |a| -> E2M1 magnitude index, round to nearest, ties to the even index, saturating at 6 (mx_round_e2m1 of mxfp4.hip, restated)
+__device__ __forceinline__ uint32_t a4_round_e2m1(float a) {
+    return a <= 0.25f ? 0u : a < 0.75f ? 1u : a <= 1.25f ? 2u : a < 1.75f ? 3u : a <= 2.5f ? 4u : a < 3.5f ? 5u : a <= 5.0f ? 6u : 7u;
+}
+
+__device__ __forceinline__ float a4_nan() { return __uint_as_float(0x7fc00000u); }
+
+__device__ __forceinline__ mxa4_v8i a4_frag(const uint4_t& v) { return mxa4_v8i{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0}; }
+
+template <int CTRL>
+__device__ __forceinline__ float a4_dpp_max(float v) {
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false)));
+}
+
+}  // namespace
+
+// ---- activation quantiser -------------------------------------------------------------------------------------------------------------
+// Workgroup = one row.  Thread t takes the 8-value units t, t + 256, ... of the row; the 4 lanes of a quad hold one block of 32.
+template <int DT>
+__global__ __launch_bounds__(256) void mxa4_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ xq, uint8_t* __restrict__ xs,
+                                                            uint8_t* __restrict__ row_flag, int K) {
+    const long m = blockIdx.x;
+    const uint16_t* xr = x + m * K;
+    uint32_t* qr = reinterpret_cast<uint32_t*>(xq + m * (K >> 1));
+    uint8_t* sr = xs + m * (K >> 5);
+    const int U = K >> 3;  // a multiple of 4: whole quads are in or out
+    int bad = 0;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        const uint4_t raw = *reinterpret_cast<const uint4_t*>(xr + (long)u * 8);
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if constexpr (DT == BIE_F16) {
+                v[2 * i] = f16_bits_to_f32(w[i] & 0xffffu);
+                v[2 * i + 1] = f16_bits_to_f32(w[i] >> 16);
+            } else {
+                v[2 * i] = bf16_bits_to_f32(w[i] & 0xffffu);
+                v[2 * i + 1] = bf16_bits_to_f32(w[i] >> 16);
+            }
+        }
+        float amax = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            amax = fmaxf(amax, fabsf(v[i]));
+            bad |= (__float_as_uint(v[i]) & 0x7f800000u) == 0x7f800000u;
+        }
+        amax = a4_dpp_max<0xB1>(amax);  // quad_perm [1, 0, 3, 2]
+        amax = a4_dpp_max<0x4E>(amax);  // quad_perm [2, 3, 0, 1]
+        uint32_t codes = 0u, scode = 0u;
+        if (amax > 0.0f) {
+            const uint32_t bits = __float_as_uint(amax);
+            const int ex = (int)(bits >> 23);
+            const int fl = ex ? ex - 127 : (31 - __builtin_clz(bits & 0x7fffffu)) - 149;  // floor(log2(amax))
+            const int e = min(max(fl - 2, -127), 127);
+            scode = (uint32_t)(e + 127);
+            const float inv = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e
+#pragma unroll
+            for (int i = 0; i < 8; i++) codes |= (a4_round_e2m1(fabsf(v[i] * inv)) | ((__float_as_uint(v[i]) >> 28) & 8u)) << (4 * i);
+        }
+        qr[u] = codes;
+        if ((u & 3) == 0) sr[u >> 2] = (uint8_t)scode;
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) row_flag[m] = (uint8_t)(bad ? 1 : 0);
+}
+
+// ---- decode form ------------------------------------------------------------------------------------------------------------------------
+// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
+// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15 and block l >> 4 of the step.  Blocks past K and rows past M enter as zero
+// codes under scale 2^0.
+template <int DT, int G>
+__global__ __launch_bounds__(256) void mxa4_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                          const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                          const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
+    __shared__ mxa4_v4f red[3][G][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const int n0 = blockIdx.x * 16;
+    const long nl = min(n0 + r16, N - 1);
+    const uint8_t* wrow = qw + nl * (K >> 1);
+    const uint8_t* srow = sc + nl * KB;
+    mxa4_v4f acc[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t b = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow) + kc);
+        int sb = __builtin_nontemporal_load(srow + kc);
+        uint4_t a[G];
+        int sa[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const long m = min(g * 16 + r16, M - 1);
+            a[g] = reinterpret_cast<const uint4_t*>(xq + m * (K >> 1))[kc];
+            sa[g] = xs[m * KB + kc];
+        }
+        if (!kin) {
+            b = uint4_t{0u, 0u, 0u, 0u};
+            sb = 127;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (!kin || g * 16 + r16 >= M) {
+                a[g] = uint4_t{0u, 0u, 0u, 0u};
+                sa[g] = 127;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(a[g]), a4_frag(b), acc[g], 4, 4, 0, sa[g], 0, sb);
+    }
+    if (wave) {
+#pragma unroll
+        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
+    }
+    __syncthreads();
+    if (wave) return;
+    // C/D: column n = lane & 15, row m = 4 (lane >> 4) + r
+    const int n = n0 + r16;
+    if (n >= N) return;
+    const bool ncol = ecol[n] == 255u;
+    const float bv = bias ? dt_traits<DT>::load(bias, n) : 0.0f;
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = g * 16 + kq * 4 + r;
+            if (m < M) {
+                float v = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
+                if (ncol || row_flag[m]) v = a4_nan();
+                if (bias) v += bv;
+                dt_traits<DT>::store(y, (long)m * N + n, v);
+            }
+        }
+    }
+}
+
+// ---- prefill form -----------------------------------------------------------------------------------------------------------------------
+constexpr int A4_BK = 128;                    // k per stage: 64 code bytes and 4 scale bytes per row
+constexpr int A4_PITCH = A4_BK / 2 + 16;      // 80 bytes per row in LDS: the 16-byte fragment reads of 16 rows fall on distinct banks
+
+// Tile (64 WM rows of x) x (64 WN columns).  LDS stage: x codes [64 WM][80], weight codes [64 WN][80], x scales [64 WM] dwords, weight
+// scales [64 WN] dwords (byte j of a row's dword = the scale of the stage's block j).  Past M / N / K: zero codes under scale 2^0.
+template <int DT, int WM, int WN>
+__global__ __launch_bounds__(256) void mxa4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                        const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                        const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
+    constexpr int BM = 64 * WM, BN = 64 * WN, ROWS = BM + BN;
+    constexpr int NLD = ROWS * 4 / 256;  // 16-byte pieces per thread and stage: row = piece / 4, quarter = piece % 4
+    constexpr int STAGE = ROWS * A4_PITCH + ROWS * 4;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    int tile_m, tile_n;
+    pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const int KB = K >> 5, KT = (K + A4_BK - 1) / A4_BK;
+
+    // load slots: pieces t, t + 256, ... of the stage image (rows 0 .. BM - 1 = x, BM .. = weights); thread t < ROWS also loads row t's scales
+    const uint8_t* csrc[NLD];
+    bool cok[NLD];
+#pragma unroll
+    for (int i = 0; i < NLD; i++) {
+        const int p = t + 256 * i, row = p >> 2;
+        if (row < BM) {
+            cok[i] = m0 + row < M;
+            csrc[i] = xq + (long)min(m0 + row, M - 1) * (K >> 1);
+        } else {
+            cok[i] = n0 + row - BM < N;
+            csrc[i] = qw + (long)min(n0 + row - BM, N - 1) * (K >> 1);
+        }
+    }
+    const bool s_thread = t < ROWS;
+    bool sok = false;
+    const uint8_t* ssrc = xs;
+    if (s_thread) {
+        if (t < BM) {
+            sok = m0 + t < M;
+            ssrc = xs + (long)min(m0 + t, M - 1) * KB;
+        } else {
+            sok = n0 + t - BM < N;
+            ssrc = sc + (long)min(n0 + t - BM, N - 1) * KB;
+        }
+    }
+    uint4_t rc[NLD];
+    uint32_t rs = 0x7f7f7f7fu;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < NLD; i++) {
+            const int kb = kt * 4 + ((t + 256 * i) & 3);
+            rc[i] = (cok[i] && kb < KB) ? *reinterpret_cast<const uint4_t*>(csrc[i] + (long)kb * 16) : uint4_t{0u, 0u, 0u, 0u};
+        }
+        if (s_thread) {
+            rs = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int kb = kt * 4 + j;
+                const uint32_t s = (sok && kb < KB) ? (uint32_t)ssrc[kb] : 127u;
+                rs |= s << (8 * j);
+            }
+        }
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < NLD; i++) {
+            const int p = t + 256 * i;
+            *reinterpret_cast<uint4_t*>(st + (p >> 2) * A4_PITCH + (p & 3) * 16) = rc[i];
+        }
+        if (s_thread) reinterpret_cast<uint32_t*>(st + ROWS * A4_PITCH)[t] = rs;
+    };
+
+    float16_t acc[WN][WM];  // [weight row block j][x row block i]: D rows = columns n of y, D columns = rows m of y
+#pragma unroll
+    for (int j = 0; j < WN; j++)
+#pragma unroll
+        for (int i = 0; i < WM; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[j][i][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * STAGE;
+        const uint32_t* ss = reinterpret_cast<const uint32_t*>(st + ROWS * A4_PITCH);
+        uint32_t sxa[WM], swa[WN];  // the row's four scale bytes, shifted so that this lane's block of k-step ks sits in byte 2 ks
+#pragma unroll
+        for (int i = 0; i < WM; i++) sxa[i] = ss[wy * 32 * WM + i * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int j = 0; j < WN; j++) swa[j] = ss[BM + wx * 32 * WN + j * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            mxa4_v8i fx[WM], fw[WN];
+#pragma unroll
+            for (int i = 0; i < WM; i++)
+                fx[i] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (wy * 32 * WM + i * 32 + rl) * A4_PITCH + (ks * 2 + hh) * 16));
+#pragma unroll
+            for (int j = 0; j < WN; j++)
+                fw[j] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (BM + wx * 32 * WN + j * 32 + rl) * A4_PITCH + (ks * 2 + hh) * 16));
+#pragma unroll
+            for (int j = 0; j < WN; j++)
+#pragma unroll
+                for (int i = 0; i < WM; i++)
+                    acc[j][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[j], fx[i], acc[j][i], 4, 4, 0, (int)((swa[j] >> (16 * ks)) & 0xffu), 0,
+                                                                                (int)((sxa[i] >> (16 * ks)) & 0xffu));
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: D column (= row m of y) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh: registers 4q .. 4q + 3 are four
+    // consecutive n of one m -> one 8-byte store where N allows it
+    const bool vec = (N & 3) == 0;
+#pragma unroll
+    for (int i = 0; i < WM; i++) {
+        const int m = m0 + wy * 32 * WM + i * 32 + rl;
+        if (m >= M) continue;
+        const bool rbad = row_flag[m] != 0;
+#pragma unroll
+        for (int j = 0; j < WN; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int n = n0 + wx * 32 * WN + j * 32 + 8 * q + 4 * hh;
+                if (n >= N) continue;
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    v[r] = acc[j][i][4 * q + r];
+                    if (n + r < N) {
+                        if (rbad || ecol[n + r] == 255u) v[r] = a4_nan();
+                        if (bias) v[r] += dt_traits<DT>::load(bias, n + r);
+                    }
+                }
+                if (vec) {
+                    uint16_t h[4];
+                    dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
+                    dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
+                    uint2_t o;
+                    o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+                    o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+                    *reinterpret_cast<uint2_t*>(reinterpret_cast<uint16_t*>(y) + (long)m * N + n) = o;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (n + r < N) dt_traits<DT>::store(y, (long)m * N + n + r, v[r]);
+                }
+            }
+    }
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The decode form serves M <= A4_DECODE_ROWS (instances of 16, 32 and 64 rows); larger M takes the prefill form.  The plan's bound was
+// measured (tools/mxfp4_a4_bench.py, profiles/mxfp4_a4_bench.jsonl, the "sweep" rows, both forms forced at M = 8 .. 64, the quantise
+// launch included): the decode form was ahead at every M <= 48 on 4096 x 4096, 4096 -> 11008 and 11008 -> 4096 in fp16 and bf16, and at
+// M = 64 on two of the three shapes (19.5 / 37.4 us against 37.4 / 80.9); on 4096 -> 11008 it was 2 % behind there (39.1 against 38.2).
+constexpr int A4_DECODE_ROWS = 64;
+constexpr int A4_PLAN_ROWS = 64;
+
+bool mxfp4_a4_decode_ok(long M) { return M >= 1 && M <= A4_DECODE_ROWS; }
+
+int mxfp4_a4_form(long M, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_A4_FORM", -1);
+    if (f == 0 && M <= A4_DECODE_ROWS) return 0;
+    if (f == 1) return 1;
+    return M <= A4_PLAN_ROWS ? 0 : 1;
+}
+
+// Workspace of bie_mxfp4_a4_linear_forward: xq [M, K/2] (16-byte aligned), xs [M, K/32], row_flag [M]
+static size_t a4_xs_offset(long M, long K) { return (size_t)((M * (K / 2) + 15) / 16 * 16); }
+static size_t a4_flag_offset(long M, long K) { return a4_xs_offset(M, K) + (size_t)(M * (K / 32)); }
+size_t mxfp4_a4_workspace_bytes(long M, long K) { return (a4_flag_offset(M, K) + (size_t)M + 15) / 16 * 16; }
+
+int mxfp4_a4_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st) {
+    const uint16_t* xp = reinterpret_cast<const uint16_t*>(x);
+    if (dtype == BIE_F16) hipLaunchKernelGGL(mxa4_quantize_kernel<BIE_F16>, dim3((unsigned)M), dim3(256), 0, st, xp, xq, xs, row_flag, (int)K);
+    else hipLaunchKernelGGL(mxa4_quantize_kernel<BIE_BF16>, dim3((unsigned)M), dim3(256), 0, st, xp, xq, xs, row_flag, (int)K);
+    return check_launch("mxa4_quantize_kernel");
+}
+
+template <int DT, int WM, int WN>
+static void a4_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                             const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const int tn = cdiv(N, 64 * WN);
+    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
+    hipLaunchKernelGGL((mxa4_gemm_kernel<DT, WM, WN>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
+}
+
+template <int DT>
+static void a4_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    // 128 x 128 tiles where they give every CU of the card (256) at least two workgroups, else 64 x 64 tiles: four times the workgroups
+    // for the small-M cells, at twice the LDS fragment reads per MFMA
+    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) a4_gemm_launch_t<DT, 2, 2>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+    else a4_gemm_launch_t<DT, 1, 1>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+}
+
+template <int DT>
+static void a4_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                                const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv(N, 16));
+    if (M <= 16) hipLaunchKernelGGL((mxa4_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else if (M <= 32) hipLaunchKernelGGL((mxa4_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else hipLaunchKernelGGL((mxa4_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+}
+
+int mxfp4_a4_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                         const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
+    if (form == 0) {
+        if (dtype == BIE_F16) a4_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        else a4_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        return check_launch("mxa4_decode_kernel");
+    }
+    if (dtype == BIE_F16) a4_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    else a4_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    return check_launch("mxa4_gemm_kernel");
+}
+
+int mxfp4_a4_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
+                            long N, long K, int dtype, int form, hipStream_t st) {
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a4_xs_offset(M, K);
+    uint8_t* rf = xq + a4_flag_offset(M, K);
+    const int rc = mxfp4_a4_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_a4_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+}
+
+}  // namespace bie

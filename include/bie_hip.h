@@ -582,6 +582,30 @@ int bie_mxfp4_form(long M, long N, long K, int dtype);
 int bie_mxfp4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
                              long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 w4a4
+ * MXFP4 weights x activations quantised to MXFP4 on the fly, contracted on the block-scaled matrix instructions (MXFP4A4LinearCuda;
+ * INTEGRATION.md, "MXFP4 W4A4 linear layer").  qweight / scales / e_col are those of the mxfp4 section above, unchanged.
+ *   xq       uint8 [M, K/2], xs uint8 [M, K/32]: x per row and block of 32 by the rule of bie_mxfp4_quantize (bit-exact for finite x)
+ *   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (the row's codes are then unspecified), else 0
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e2m1(xq[m,k]) * e2m1(qweight[n,k])) + bias[n] ): block sums exact,
+ *              the sum over blocks in fp32 in any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ * bie_mxfp4_quantize_act: x [M, K] (dtype 0/1, 16-byte aligned) -> xq (16-byte aligned), xs, row_flag.
+ * bie_mxfp4_a4_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP4_A4_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mxfp4_a4_workspace_bytes: the bytes bie_mxfp4_a4_linear_forward needs for xq, xs and row_flag (any form); 0 for a shape the layer
+ *   refuses.  Host only.  bie_mxfp4_a4_gemm needs no workspace (NULL is accepted).
+ * bie_mxfp4_a4_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction.  form -1 =
+ *   bie_mxfp4_a4_form.  e_col (bie_mxfp4_col_exp) is required by both forms.
+ * bie_mxfp4_a4_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call; nothing synchronises with the host. */
+int bie_mxfp4_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream);
+int bie_mxfp4_a4_form(long M, long N, long K, int dtype);
+size_t bie_mxfp4_a4_workspace_bytes(long M, long N, long K, int form);
+int bie_mxfp4_a4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                                void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mxfp4_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                      const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
