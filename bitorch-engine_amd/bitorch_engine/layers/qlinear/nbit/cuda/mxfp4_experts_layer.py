@@ -1,0 +1,146 @@
+"""MXFP4ExpertsLinearCuda: the stacked expert projection of a mixture-of-experts MLP, MXFP4 weights x fp16 / bf16 activations on the
+kernels of csrc/mxfp4_moe.hip.
+
+  y[t, s] = dt( x_row . W[idx[t, s]]^T + bias[idx[t, s]] ),   W[e, n, k] = e2m1(qweight nibble) * 2^(scales[e, n, k // 32] - 127)
+  x_row = x[t] for x [T, K] (every slot of a token reads the token's row) or x[t, s] for x [T, S, K];  y[t, s] = 0 for a skipped slot
+  (idx outside [0, E), -1 by convention)
+
+qweight uint8 [E, N, K/2] and scales uint8 [E, N, K/32] are byte for byte the `blocks` / `scales` of the expert tensors of gpt-oss-style
+MXFP4 checkpoints (set_mx_weight).  e_col is derived from scales and not saved.
+
+Training (train() with the latent weight): re-quantised on every call, the forward runs on the kernels and the backward is the
+straight-through composition in torch, expert by expert.  Eval: the packed weight; a forward with grad enabled is differentiable in x
+(and bias)."""
+import math
+import typing
+
+import torch
+from torch import nn
+from torch.autograd import Function
+
+from bitorch_engine.utils.safe_import import import_extension
+from bitorch_engine.layers.qlinear.ternary.layer import TernaryWeightState
+
+mxfp4_experts_cuda = import_extension("mxfp4_experts_cuda")
+
+
+class MXFP4ExpertsLinearForward(Function):
+    """Forward: the expert kernels.  Backward (straight-through estimator, in fp32, cast to the dtype), over the live pairs p of expert e:
+      grad_x[row(p)] += gy[p] . W[e]        (summed over a token's slots when x is [T, K])
+      grad_weight[e]  = gy[pairs of e]^T . x_rows
+      grad_bias[e]    = sum gy[pairs of e]
+    Skipped slots contribute nothing.  A loop over the experts in torch: not a hot path."""
+
+    @staticmethod
+    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col):
+        ctx.save_for_backward(x, idx, qweight, scales)
+        return mxfp4_experts_cuda.forward(x, idx, qweight, scales, bias, e_col)
+
+    @staticmethod
+    @typing.no_type_check
+    def backward(ctx, gy):
+        x, idx, qweight, scales = ctx.saved_tensors
+        E, N, K = qweight.shape[0], qweight.shape[1], qweight.shape[2] * 2
+        T, S = idx.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        g = gy.reshape(T * S, N).float()
+        flat = idx.reshape(-1).long()
+        xr = (x if x.dim() == 3 else x[:, None, :].expand(T, S, K)).reshape(T * S, K).float()
+        gx = torch.zeros((T * S, K), dtype=torch.float32, device=gy.device) if need_x else None
+        gw = torch.zeros((E, N, K), dtype=torch.float32, device=gy.device) if need_w else None
+        gb = torch.zeros((E, N), dtype=torch.float32, device=gy.device) if need_b else None
+        W = mxfp4_experts_cuda.dequant(qweight, scales, torch.float32) if need_x else None
+        for e in range(E):
+            rows = (flat == e).nonzero().reshape(-1)
+            if rows.numel() == 0:
+                continue
+            ge = g[rows]
+            if need_x:
+                gx[rows] = ge.mm(W[e])
+            if need_w:
+                gw[e] = ge.t().mm(xr[rows])
+            if need_b:
+                gb[e] = ge.sum(0)
+        if need_x:
+            gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
+        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
+
+
+class MXFP4ExpertsLinearCuda(TernaryWeightState, nn.Module):
+    """Float latent `weight` [E, N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight),
+    the packed codes `qweight` uint8 [E, N, K/2] and E8M0 `scales` uint8 [E, N, K/32] (buffers), an optional `bias` [E, N].
+    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16."""
+
+    def __init__(self, num_experts: int, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
+                 dtype: torch.dtype = torch.float16) -> None:
+        super().__init__()
+        if input_features % 32 or input_features <= 0 or input_features > (1 << 20) or out_features <= 0 or not 1 <= num_experts <= 1024:
+            raise ValueError(f"mxfp4 experts need input_features % 32 == 0, 32 <= input_features <= 2^20, out_features >= 1 and "
+                             f"1 <= num_experts <= 1024 (got {input_features}, {out_features}, {num_experts})")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError(f"mxfp4 experts compute in fp16 or bf16 (got {dtype})")
+        self.num_experts, self.input_features, self.output_features = num_experts, input_features, out_features
+        self.device, self.dtype = device, dtype
+        E, N, K = num_experts, out_features, input_features
+        w = torch.empty((E, N, K), dtype=dtype, device=device)
+        for e in range(E):
+            nn.init.kaiming_uniform_(w[e], a=math.sqrt(5))
+        self.weight = nn.Parameter(w)
+        self.bias = nn.Parameter(torch.zeros((E, N), dtype=dtype, device=device)) if bias else None
+        self.register_buffer("qweight", torch.zeros((E, N, K // 2), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.zeros((E, N, K // 32), dtype=torch.uint8, device=device))
+        self.register_buffer("e_col", torch.zeros((E, N), dtype=torch.uint8, device=device), persistent=False)
+        self._packed = False  # qweight / scales / e_col hold the current weight (or a loaded / set MXFP4 weight)
+
+    def _state_device(self) -> torch.device:
+        return self.qweight.device
+
+    def prepare_params(self) -> None:
+        """qweight / scales from the latent weight (kept as they are for a layer that holds only the packed weight), then e_col."""
+        with torch.no_grad():
+            if self.weight is not None:
+                self.qweight, self.scales = mxfp4_experts_cuda.quantize(self.weight)
+            self.e_col = mxfp4_experts_cuda.col_exp(self.scales)
+        self._packed = True
+
+    def set_mx_weight(self, blocks: torch.Tensor, scales: torch.Tensor) -> None:
+        """Load the experts' MXFP4 weight: blocks uint8 [E, N, K/32, 16] (the checkpoint layout) or [E, N, K/2], scales uint8
+        [E, N, K/32].  The latent weight is dropped, so the layer computes with exactly these values in every mode."""
+        E, N, K = self.num_experts, self.output_features, self.input_features
+        if blocks.dtype != torch.uint8 or scales.dtype != torch.uint8:
+            raise ValueError("set_mx_weight: blocks and scales must be uint8")
+        if tuple(blocks.shape) == (E, N, K // 32, 16):
+            blocks = blocks.reshape(E, N, K // 2)
+        if tuple(blocks.shape) != (E, N, K // 2) or tuple(scales.shape) != (E, N, K // 32):
+            raise ValueError(f"set_mx_weight: blocks {tuple(blocks.shape)} / scales {tuple(scales.shape)} do not match [E={E}, N={N}, K={K}]")
+        dev = self.qweight.device
+        self.qweight = blocks.to(dev).contiguous()
+        self.scales = scales.to(dev).contiguous()
+        self.weight = None
+        self.prepare_params()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        self._packed = False  # e_col is re-derived (and, with a latent weight, qweight / scales) before the next packed forward
+
+    def forward(self, x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        """x [T, K] or [T, S, K], idx int32 [T, S] (other integer types are converted) -> [T, S, N]."""
+        assert x.size(-1) == self.input_features, f"Weight and input tensor mismatch: {x.size(-1)} != {self.input_features}"
+        assert x.dtype == self.dtype, f"dtype mismatch. Expected: '{self.dtype}', but '{x.dtype}' found"
+        if idx.dtype != torch.int32:
+            idx = idx.to(torch.int32)
+        training = self.training and self.weight is not None
+        if training:  # re-quantised every call: the weight may have changed since the last one
+            self._packed = False
+            with torch.no_grad():
+                qweight, scales = mxfp4_experts_cuda.quantize(self.weight)
+            e_col = None  # computed by the forward where the prefill form needs it
+        else:
+            if not self._packed:
+                self.prepare_params()
+            qweight, scales, e_col = self.qweight, self.scales, self.e_col
+        grad = torch.is_grad_enabled() and (x.requires_grad or (training and self.weight.requires_grad)
+                                            or (self.bias is not None and self.bias.requires_grad))
+        if not grad:
+            return mxfp4_experts_cuda.forward(x, idx, qweight, scales, self.bias, e_col)
+        return MXFP4ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col)

@@ -16,23 +16,11 @@
 // fragment is 4 code bytes = 4 converts.  Each column is rebiased by its largest scale code e_col[n] (bie_mxfp4_col_exp, computed once
 // at load time): fragments hold e2m1 * 2^(s - e_col[n]) <= 6 and the fp32 epilogue multiplies by 2^(e_col[n] - 127).  A column with a
 // scale-255 block has e_col = 255, which makes the whole column NaN in the epilogue.
-#include "mfma_pipe.cuh"
+#include "mxfp4_common.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-typedef __bf16 mx_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 mx_half8_t __attribute__((ext_vector_type(8)));
-
-// E8M0 -> fp32: 2^(s - 127), code 0 the subnormal 2^-127 (not 0.0), code 255 NaN (not +inf, which the plain s << 23 would give)
-__device__ __forceinline__ float e8m0_f32(uint32_t s) { return __uint_as_float(s == 0u ? 0x00400000u : s == 255u ? 0x7fc00000u : s << 23); }
-
-// 2^d for d <= 0 as the convert's scale: 0 below 2^-126 (e2m1 * 2^d then lies below every fp16 / bf16 normal the fragments keep)
-__device__ __forceinline__ float mx_rebias(uint32_t s, uint32_t e) {
-    const int d = (int)s - (int)e;
-    return __uint_as_float(d < -126 ? 0u : (uint32_t)(d + 127) << 23);
-}
 
 __device__ __forceinline__ float mx_e2m1(uint32_t c) {  // the code's value as fp32 bits: 0, 0.5, then (1 + m / 2) * 2^(e - 1)
     const uint32_t i = c & 7u;
@@ -106,34 +94,6 @@ __global__ __launch_bounds__(256) void mx_col_exp_kernel(const uint8_t* __restri
 }
 
 // ---- decode form --------------------------------------------------------------------------------------------------------------------
-template <int DT> struct mx_pair;
-template <> struct mx_pair<BIE_BF16> {
-    typedef bf16x2_t t;
-    template <int SEL>
-    static __device__ __forceinline__ t cvt(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, 1.0f, SEL); }
-    static __device__ __forceinline__ float dot(t a, uint32_t b, float c) { return __builtin_amdgcn_fdot2_f32_bf16(a, __builtin_bit_cast(t, b), c, false); }
-};
-template <> struct mx_pair<BIE_F16> {
-    typedef half2_t t;
-    template <int SEL>
-    static __device__ __forceinline__ t cvt(uint32_t w) { return __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, 1.0f, SEL); }
-    static __device__ __forceinline__ float dot(t a, uint32_t b, float c) { return __builtin_amdgcn_fdot2(a, __builtin_bit_cast(t, b), c, false); }
-};
-
-template <int CTRL, int RMASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RMASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {  // wave_sum_dpp's network (bie_common.h) on fp32; the total of lane 63
-    v = dpp_add<0xB1, 0xf>(v);
-    v = dpp_add<0x4E, 0xf>(v);
-    v = dpp_add<0x141, 0xf>(v);
-    v = dpp_add<0x140, 0xf>(v);
-    v = dpp_add<0x142, 0xa>(v);
-    v = dpp_add<0x143, 0xc>(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 // Workgroup: columns C * blockIdx.x .. + C - 1 (clamped reads past N, never stored), rows 0 .. M - 1 (M <= R).  Thread t takes the
 // 16-value units u = t, t + 256, ... of K: per column 8 code bytes and the scale byte of block u / 2.
 template <int DT, int R, int C>
@@ -217,26 +177,6 @@ constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 64;
 constexpr int MX_APITCH = MX_BK * 2 + 16;  // bytes per x row in LDS (16-byte pad: the fragment reads of 32 rows spread over the banks)
 constexpr int MX_BPITCH = 36;              // bytes per weight row: 32 code bytes + 4 (9 dwords, the 32 rows of a read on distinct banks)
 constexpr int MX_STAGE = MX_BM * MX_APITCH + MX_BN * MX_BPITCH + MX_BN * 2 * 4;  // x, codes, the two fp32 rebiased scales per row
-
-template <int DT> struct mx_frag;
-template <> struct mx_frag<BIE_BF16> {
-    typedef mx_bf16x8_t t;
-    static __device__ __forceinline__ t cvt(uint32_t w, float s) {
-        const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 1);
-        const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 3);
-        return t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-    }
-    static __device__ __forceinline__ float16_t mfma(const t& a, const t& b, const float16_t& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct mx_frag<BIE_F16> {
-    typedef mx_half8_t t;
-    static __device__ __forceinline__ t cvt(uint32_t w, float s) {
-        const half2_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 1);
-        const half2_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 3);
-        return t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-    }
-    static __device__ __forceinline__ float16_t mfma(const t& a, const t& b, const float16_t& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
 
 // 4 waves as 2 x 2, wave tile 64 x 64 (2 x 2 MFMA tiles).  Per 64-k stage a thread loads 4 x 16 bytes of x, 16 code bytes and one
 // scale byte into registers while the MFMAs run on the other LDS buffer, then writes them (the scale already rebiased to fp32).

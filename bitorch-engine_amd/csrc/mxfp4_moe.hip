@@ -1,0 +1,370 @@
+// MXFP4 mixture-of-experts expert GEMM for gfx950: the weights of mxfp4.hip stacked per expert, every (token, slot) pair contracted with
+// the expert its index names (include/bie_hip.h, INTEGRATION.md "MXFP4 mixture-of-experts layer").  No reference implementation exists.
+//
+//   T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p]
+//   qweight uint8 [E, N, K/2], scales uint8 [E, N, K/32], e_col uint8 [E, N], bias [E, N] or NULL: mxfp4.hip's format on the [E * N, K] view
+//   y[p, :] = dt( x_row(p) . W[idx[p]]^T + bias[idx[p]] ),  x_row(p) = x[p / S] (x_per_pair = 0, x is [T, K]) or x[p] (x_per_pair = 1, [P, K])
+//   y[p, :] = 0 where idx[p] is outside [0, E): the index is compared before any address is formed from it
+//
+// A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone, whatever the
+// other pairs are and wherever routing places the row.  Every expert and row offset is 64-bit.  Nothing synchronises with the host: the
+// grids are sized from P and E, surplus workgroups leave after reading the tile count the routing kernel wrote.
+//
+// Routed decode form (mxm_decode_kernel, one launch): a workgroup per pair and C output columns, the arithmetic of mx_decode_kernel for
+// one row (v_cvt_scalef32_pk_*_fp4 at scale 1, v_dot2_f32_*, the block scale on the fp32 partial, DPP sums).  It reads idx[p] and
+// offsets into that expert's rows.  Keeps the fp32 range of W, needs neither e_col nor a workspace.
+// Grouped prefill form (two launches):
+//   mxm_route_kernel, one workgroup: an LDS histogram of the pairs over the experts (the skipped pairs in a bin of their own), an
+//   exclusive scan, the tile table (expert, first entry, rows) with every expert's segment cut into row tiles of MXM_BM, and the pair
+//   list ordered by expert.  The order of the pairs inside a segment is that of the LDS atomics' arrival; no row of y depends on it.
+//   mxm_gemm_kernel: mx_gemm_kernel's 128 x 128 tile on v_mfma_f32_32x32x16_{f16,bf16} (packed codes staged in LDS, converted in
+//   registers, columns rebiased by e_col[e, n]).  A row tile belongs to one expert and gathers its x rows through the pair list, each
+//   row in whole 16-byte pieces; rows past the segment load as zero and are not stored; the epilogue scatters row r to y[pair r].  The
+//   tiles of the skipped bin run no K loop and store zeros.
+#include "mxfp4_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// ---- routed decode form -------------------------------------------------------------------------------------------------------------------
+// Workgroup: pair blockIdx.y, columns C * blockIdx.x .. + C - 1 of its expert (clamped reads past N, never stored).  Thread t takes the
+// 16-value units u = t, t + 256, ... of K, as in mx_decode_kernel.
+template <int DT, int C>
+__global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw,
+                                                         const uint8_t* __restrict__ sc, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                         int N, int K, int x_per_pair) {
+    typedef mx_pair<DT> P;
+    __shared__ float red[4][C];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.y, n0 = blockIdx.x * C;
+    const int e = idx[p];
+    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
+        if (threadIdx.x < C && n0 + (int)threadIdx.x < N) dt_traits<DT>::store(y, (long)p * N + n0 + threadIdx.x, 0.0f);
+        return;
+    }
+    const int U = K >> 4, KB = K >> 5;
+    const uint16_t* xr = x + (long)(x_per_pair ? p : p / S) * K;
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+    const uint8_t* wrow[C];
+    const uint8_t* srow[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const long n = r0 + min(n0 + c, N - 1);
+        wrow[c] = qw + n * (K >> 1);
+        srow[c] = sc + n * KB;
+    }
+    float acc[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) acc[c] = 0.0f;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint2_t wb[C];
+        uint32_t sb[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            wb[c] = __builtin_nontemporal_load(reinterpret_cast<const uint2_t*>(wrow[c]) + u);
+            sb[c] = __builtin_nontemporal_load(srow[c] + (u >> 1));
+        }
+        const uint4_t* xp = reinterpret_cast<const uint4_t*>(xr) + 2 * u;
+        const uint4_t x0 = xp[0], x1 = xp[1];
+        const uint32_t xv[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            typename P::t wv[8];
+            wv[0] = P::template cvt<0>(wb[c].x); wv[1] = P::template cvt<1>(wb[c].x);
+            wv[2] = P::template cvt<2>(wb[c].x); wv[3] = P::template cvt<3>(wb[c].x);
+            wv[4] = P::template cvt<0>(wb[c].y); wv[5] = P::template cvt<1>(wb[c].y);
+            wv[6] = P::template cvt<2>(wb[c].y); wv[7] = P::template cvt<3>(wb[c].y);
+            float s = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; j++) s = P::dot(wv[j], xv[j], s);
+            acc[c] += s * e8m0_f32(sb[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const float v = wave_sum_f32(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < C) {
+        const int c = threadIdx.x, n = n0 + c;
+        if (n < N) {
+            float v = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
+            dt_traits<DT>::store(y, (long)p * N + n, v);
+        }
+    }
+}
+
+// ---- grouped prefill form: routing --------------------------------------------------------------------------------------------------------
+constexpr int MXM_BM = 128, MXM_BN = 128, MXM_BK = 64;
+constexpr int MXM_MAX_E = 1024;
+constexpr int MXM_HEAD = 4;  // int32 words before the tile table: [0] the tile count
+
+// Workspace (int32): head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P].
+// max_tiles bounds sum_e ceil(count_e / BM) + ceil(skipped / BM): every tile holds a pair, and at most one tile per bin is not full.
+static long mxm_max_tiles(long P, long E) { return P < P / MXM_BM + E + 1 ? P : P / MXM_BM + E + 1; }
+
+// One workgroup of 1024 threads, bin e of the scan on thread e.  Two passes over idx: count, then place.  One workgroup keeps the
+// histogram and the cursors in LDS and needs no counters zeroed between calls; its cost is P / 1024 iterations per thread and pass on
+// one CU before the GEMM can start: 16 at P = 16384 (15 us against the GEMM's 988 us at 2880 -> 5760: profiles/mxfp4_moe_kernel_stats.csv), 4096 at the largest
+// admitted P = 2^22, where the routing is expected to take milliseconds.  That is a known limit: a multi-workgroup routing (per-workgroup
+// LDS histograms merged with vector atomics) is the follow-up if calls of millions of pairs matter.
+__global__ __launch_bounds__(1024) void mxm_route_kernel(const int32_t* __restrict__ idx, int32_t* __restrict__ ws, int P, int E, int max_tiles) {
+    __shared__ int cnt[MXM_MAX_E], cur[MXM_MAX_E];
+    __shared__ int poff[MXM_MAX_E + 1], toff[MXM_MAX_E + 1];  // exclusive pair / tile offsets of the bins; [E] = the skipped bin's
+    __shared__ unsigned long long scan[2][MXM_MAX_E];
+    __shared__ int nskip, curskip;
+    const int t = threadIdx.x;
+    cnt[t] = 0;
+    cur[t] = 0;
+    if (t == 0) nskip = 0, curskip = 0;
+    __syncthreads();
+    for (int p = t; p < P; p += 1024) {
+        const int e = idx[p];
+        atomicAdd((unsigned)e < (unsigned)E ? &cnt[e] : &nskip, 1);
+    }
+    __syncthreads();
+    // inclusive scan of (tiles << 32 | pairs) over the 1024 bins (bins from E on are empty)
+    const int c = cnt[t];
+    const unsigned long long v = ((unsigned long long)((c + MXM_BM - 1) / MXM_BM) << 32) | (unsigned)c;
+    scan[0][t] = v;
+    __syncthreads();
+    int b = 0;
+    for (int d = 1; d < MXM_MAX_E; d <<= 1, b ^= 1) {
+        unsigned long long a = scan[b][t];
+        if (t >= d) a += scan[b][t - d];
+        scan[b ^ 1][t] = a;
+        __syncthreads();
+    }
+    const unsigned long long inc = scan[b][t];
+    poff[t] = (int)(uint32_t)(inc - v);
+    toff[t] = (int)((inc - v) >> 32);
+    if (t == MXM_MAX_E - 1) {
+        poff[MXM_MAX_E] = (int)(uint32_t)inc;
+        toff[MXM_MAX_E] = (int)(inc >> 32);
+    }
+    __syncthreads();
+    const int live_tiles = toff[E], live_pairs = poff[E];
+    const int n_tiles = live_tiles + (nskip + MXM_BM - 1) / MXM_BM;  // <= max_tiles (see mxm_max_tiles)
+    int32_t* tile_expert = ws + MXM_HEAD;
+    int32_t* tile_first = tile_expert + max_tiles;
+    int32_t* tile_rows = tile_first + max_tiles;
+    int32_t* list = tile_rows + max_tiles;
+    if (t == 0) ws[0] = n_tiles;
+    for (int i = t; i < n_tiles; i += 1024) {
+        int e, first, left;
+        if (i >= live_tiles) {
+            e = E;
+            first = live_pairs + (i - live_tiles) * MXM_BM;
+            left = live_pairs + nskip - first;
+        } else {  // the last bin of [0, E) whose first tile is at or before i: the one that holds tile i (empty bins share an offset)
+            int lo = 0, hi = E - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (toff[mid] <= i) lo = mid; else hi = mid - 1;
+            }
+            e = lo;
+            first = poff[e] + (i - toff[e]) * MXM_BM;
+            left = poff[e] + cnt[e] - first;
+        }
+        tile_expert[i] = e;
+        tile_first[i] = first;
+        tile_rows[i] = left < MXM_BM ? left : MXM_BM;
+    }
+    for (int p = t; p < P; p += 1024) {
+        const int e = idx[p];
+        const bool live = (unsigned)e < (unsigned)E;
+        const int at = atomicAdd(live ? &cur[e] : &curskip, 1);
+        list[(live ? poff[e] : live_pairs) + at] = p;
+    }
+}
+
+// ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
+constexpr int MXM_APITCH = MXM_BK * 2 + 16;  // as MX_APITCH / MX_BPITCH / MX_STAGE of mxfp4.hip
+constexpr int MXM_BPITCH = 36;
+constexpr int MXM_STAGE = MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH + MXM_BN * 2 * 4;
+
+// 4 waves as 2 x 2, wave tile 64 x 64, the stage pipeline of mx_gemm_kernel.  Workgroup -> (row tile, column tile): the workgroups of
+// one XCD (blockIdx.x & 7) walk the row tiles of one column tile after another, so the tiles of one expert, which follow each other in
+// the table, find the expert's 128 columns of weights in that XCD's L2.
+template <int DT>
+__global__ __launch_bounds__(256) void mxm_gemm_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw,
+                                                       const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol, const void* __restrict__ bias,
+                                                       void* __restrict__ y, int S, int E, int N, int K, int x_per_pair, int max_tiles) {
+    typedef mx_frag<DT> F;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MXM_STAGE];
+    __shared__ int prow[MXM_BM];  // the tile's pairs, -1 past the segment
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    int bid = blockIdx.x;
+    {
+        const int nblk = gridDim.x, xcd = bid & 7, per = nblk >> 3, rem = nblk & 7;
+        bid = xcd * per + (xcd < rem ? xcd : rem) + (bid >> 3);
+    }
+    const int tile_m = bid % max_tiles, tile_n = bid / max_tiles;
+    if (tile_m >= ws[0]) return;  // a surplus workgroup (uniform)
+    const int e = ws[MXM_HEAD + tile_m], first = ws[MXM_HEAD + max_tiles + tile_m], rows = ws[MXM_HEAD + 2 * max_tiles + tile_m];
+    const int32_t* list = ws + MXM_HEAD + 3 * (long)max_tiles;
+    if (t < MXM_BM) prow[t] = t < rows ? list[first + t] : -1;
+    __syncthreads();
+    const int n0 = tile_n * MXM_BN;
+    if (e >= E) {  // the skipped bin: zero rows
+        for (int i = t; i < MXM_BM * MXM_BN; i += 256) {
+            const int p = prow[i / MXM_BN], n = n0 + i % MXM_BN;
+            if (p >= 0 && n < N) dt_traits<DT>::store(y, (long)p * N + n, 0.0f);
+        }
+        return;
+    }
+    const int KT = (K + MXM_BK - 1) / MXM_BK, KB = K >> 5;
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+
+    // this thread's load slots
+    const int bn = t >> 1, bh = t & 1;  // weight row bn of the tile, 16-byte half bh; scale block bh of the stage
+    const int nb = n0 + bn;
+    const bool nb_ok = nb < N;
+    const uint8_t* wsrc = qw + (r0 + min(nb, N - 1)) * (K >> 1) + bh * 16;
+    const uint8_t* ssrc = sc + (r0 + min(nb, N - 1)) * KB + bh;
+    const uint32_t ec = nb_ok ? ecol[r0 + nb] : 0u;
+    const uint16_t* xrow[4];  // the gathered x rows of this thread's four 16-byte pieces per stage
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int p = prow[(t + 256 * i) >> 3];
+        xrow[i] = p >= 0 ? x + (long)(x_per_pair ? p : p / S) * K + (t & 7) * 8 : nullptr;
+    }
+    uint4_t ra[4], rb;
+    float rs;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            ra[i] = (xrow[i] && kt * MXM_BK + (t & 7) * 8 < K) ? *reinterpret_cast<const uint4_t*>(xrow[i] + kt * MXM_BK) : uint4_t{0u, 0u, 0u, 0u};
+        const bool kin = kt * MXM_BK + bh * 32 < K;
+        rb = (nb_ok && kin) ? __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wsrc + kt * 32)) : uint4_t{0u, 0u, 0u, 0u};
+        rs = (nb_ok && kin) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), ec) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MXM_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MXM_APITCH + c16 * 16) = ra[i];
+        }
+        uint32_t* wb = reinterpret_cast<uint32_t*>(st + MXM_BM * MXM_APITCH + bn * MXM_BPITCH + bh * 16);
+        wb[0] = rb.x; wb[1] = rb.y; wb[2] = rb.z; wb[3] = rb.w;
+        reinterpret_cast<float*>(st + MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH)[bn * 2 + bh] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * MXM_STAGE;
+        const float* ss = reinterpret_cast<const float*>(st + MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH);
+#pragma unroll
+        for (int ks = 0; ks < MXM_BK / 16; ks++) {
+            typename F::t a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MXM_APITCH + ks * 32 + hh * 16));
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int n = wx * 64 + j * 32 + rl;
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(st + MXM_BM * MXM_APITCH + n * MXM_BPITCH + ks * 8 + hh * 4);
+                b[j] = F::cvt(w, ss[n * 2 + (ks >> 1)]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: column n = lane & 31, tile row (r & 3) + 8 (r >> 2) + 4 hh, scattered to y[pair of the row]
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int n = n0 + wx * 64 + j * 32 + rl;
+        if (n >= N) continue;
+        const float cs = e8m0_f32(ecol[r0 + n]);
+        const float bv = bias ? dt_traits<DT>::load(bias, r0 + n) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int p = prow[wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
+                if (p >= 0) {
+                    float v = acc[i][j][r] * cs;
+                    if (bias) v += bv;
+                    dt_traits<DT>::store(y, (long)p * N + n, v);
+                }
+            }
+    }
+}
+
+// ---- plan and launcher --------------------------------------------------------------------------------------------------------------------
+// The routed decode form exists for P <= MXM_DECODE_PAIRS (its grid's second dimension).  The plan's bound was measured
+// (tools/mxfp4_moe_bench.py, profiles/mxfp4_moe_bench.jsonl, the `sweep` rows: gpt-oss-20b's 2880 -> 5760 and 2880 -> 2880 at E = 32
+// and 2880 -> 5760 at E = 128, fp16 and bf16, P = 1 .. 256).  The decode form was ahead at every P <= 64 on every row (at P = 64:
+// 138 / 69 us against 197 / 97 at E = 32, 139 against 385 - 398 at E = 128).  Beyond that it depends on the pairs per expert: at
+// E = 32 the grouped form leads from P = 128 on (277 against 209 - 211 us at 5760, 132 against 102 - 103 at 2880; 560 against 215 at
+// P = 256), at E = 128 the decode form still leads at P = 128 and 256 (279 against 569 - 592 us, 564 against 774 - 779): the grouped
+// form streams the whole weight of every expert that has a pair through a mostly empty row tile, the decode form the weight of
+// every pair.  So the plan takes the decode form for P <= 64, and up to P = 256 (the end of the sweep) while P <= 2 E.  (The rows' `plan`
+// column is the plan of the build that measured them, P <= 64 alone; the E = 128 rows are what added the second clause.)
+constexpr int MXM_DECODE_PAIRS = 1024;
+constexpr int MXM_PLAN_PAIRS = 64, MXM_PLAN_PAIRS_SPARSE = 256;
+
+int mxfp4_moe_form(long P, long E, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_MOE_FORM", -1);
+    if (f == 0 && P <= MXM_DECODE_PAIRS) return 0;
+    if (f == 1) return 1;
+    return (P <= MXM_PLAN_PAIRS || (P <= MXM_PLAN_PAIRS_SPARSE && P <= 2 * E)) ? 0 : 1;
+}
+
+bool mxfp4_moe_decode_ok(long P) { return P >= 1 && P <= MXM_DECODE_PAIRS; }
+
+size_t mxfp4_moe_workspace_bytes(long P, long E) {
+    const size_t words = (size_t)MXM_HEAD + 3 * (size_t)mxm_max_tiles(P, E) + (size_t)P;
+    return (words * 4 + 15) / 16 * 16;
+}
+
+int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                             void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
+    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
+    const long P = T * S;
+    if (form == 0) {
+        constexpr int C = 4;
+        const dim3 grid((unsigned)cdivl(N, C), (unsigned)P);
+        if (dtype == BIE_F16)
+            hipLaunchKernelGGL((mxm_decode_kernel<BIE_F16, C>), grid, dim3(256), 0, st, xs, idx, qw, sc, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair);
+        else
+            hipLaunchKernelGGL((mxm_decode_kernel<BIE_BF16, C>), grid, dim3(256), 0, st, xs, idx, qw, sc, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair);
+        return check_launch("mxm_decode_kernel");
+    }
+    int32_t* ws = reinterpret_cast<int32_t*>(workspace);
+    const int max_tiles = (int)mxm_max_tiles(P, E);
+    hipLaunchKernelGGL(mxm_route_kernel, dim3(1), dim3(1024), 0, st, idx, ws, (int)P, (int)E, max_tiles);
+    int rc = check_launch("mxm_route_kernel");
+    if (rc) return rc;
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, MXM_BN)));
+    if (dtype == BIE_F16)
+        hipLaunchKernelGGL(mxm_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
+    else
+        hipLaunchKernelGGL(mxm_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
+    return check_launch("mxm_gemm_kernel");
+}
+
+}  // namespace bie

@@ -606,6 +606,29 @@ int bie_mxfp4_a4_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp4_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 mixture of experts
+ * The expert GEMM of a mixture-of-experts MLP on stacked MXFP4 weights (MXFP4ExpertsLinearCuda, MXFP4MoECuda; INTEGRATION.md, "MXFP4
+ * mixture-of-experts layer").  T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p].
+ *   qweight  uint8 [E, N, K/2], scales uint8 [E, N, K/32], e_col uint8 [E, N], bias [E, N] in the dtype or NULL: the mxfp4 section's
+ *            format on the [E * N, K] view (quantise / dequant / col_exp are that section's entries on that view)
+ *   idx      int32 [T, S];  x [T, K] (x_per_pair = 0: every slot of a token reads the token's row) or [P, K] (x_per_pair = 1)
+ *   y[p, :]  = dt( x_row(p) . W[idx[p]]^T + bias[idx[p]] ), each row by the mxfp4 section's contract; y[p, :] = 0 where idx[p] is outside
+ *              [0, E) (a skipped slot; -1 by convention), and nothing is read through such an index
+ *   A row of y depends on its own pair only; two runs of one call are bit-identical.
+ *   K % 32 == 0, 32 <= K <= 2^20; N >= 1; 1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22.
+ * bie_mxfp4_moe_form: 0 = routed decode form (one launch, P <= 1024), 1 = grouped prefill form (a routing kernel and a grouped MFMA
+ *   GEMM).  The plan takes the decode form for P <= 64, and for P <= 256 while P <= 2 E (measured); BIE_MXFP4_MOE_FORM=0/1 forces a
+ *   form (0 only where P <= 1024).  Host only.
+ * bie_mxfp4_moe_workspace_bytes: the bytes the prefill form needs (tile table and pair list); 0 for refused P / E.  Host only.
+ * bie_mxfp4_moe_forward: form -1 = bie_mxfp4_moe_form.  The prefill form needs e_col and the workspace (16-byte aligned; it need not
+ *   be initialised); the decode form takes NULL for both.  x and qweight 16-byte aligned.  The precision notes of
+ *   bie_mxfp4_linear_forward's two forms hold.  Every argument is validated on the host before any device call; nothing synchronises
+ *   with the host. */
+int bie_mxfp4_moe_form(long P, long E, long N, long K, int dtype);
+size_t bie_mxfp4_moe_workspace_bytes(long P, long E);
+int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
