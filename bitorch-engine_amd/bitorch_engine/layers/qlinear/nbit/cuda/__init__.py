@@ -5,4 +5,5 @@ from .mpq_list import MPQForwardList, MBWQExl2ForwardList
 from .mxfp4_layer import MXFP4LinearCuda, MXFP4LinearForward
 from .mxfp4_a4_layer import MXFP4A4LinearCuda, MXFP4A4LinearForward
 from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda, MXFP4ExpertsLinearForward
+from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda, MXFP4A4ExpertsLinearForward
 from .mxfp4_moe_layer import MXFP4MoECuda

@@ -9,11 +9,16 @@ mixture-of-experts layer").  For x [T, hidden] (leading dimensions are flattened
   y = dt( sum_s w[t, s] * o[t, s] )                      in fp32, rounded once
 
 The two expert projections run on the kernels of csrc/mxfp4_moe.hip; the routing stays on the device, so the block can be captured in
-a graph.  The activation and the combine are torch ops (fusing them into the kernels is a follow-up)."""
+a graph.  The activation and the combine are torch ops (fusing them into the kernels is a follow-up).
+
+activations="mxfp4" ("MXFP4 W4A4 mixture-of-experts layer"): gate_up and down are MXFP4A4ExpertsLinearCuda, which
+quantise x and a to MXFP4 per row and block of 32 and contract on the block-scaled matrix instructions (csrc/mxfp4_moe_a4.hip); the
+router, the top-k softmax, the SwiGLU and the combine are the same ops.  The default "dtype" is the block above, untouched."""
 import torch
 from torch import nn
 
 from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda
+from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda
 
 
 def swiglu(h: torch.Tensor, limit: float, alpha: float) -> torch.Tensor:
@@ -35,15 +40,19 @@ class MXFP4MoECuda(nn.Module):
     is what one shard of an expert-parallel group computes before the shards' outputs are summed."""
 
     def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, bias: bool = True, swiglu_limit: float = 7.0,
-                 swiglu_alpha: float = 1.702, device: torch.device = None, dtype: torch.dtype = torch.bfloat16) -> None:
+                 swiglu_alpha: float = 1.702, device: torch.device = None, dtype: torch.dtype = torch.bfloat16, activations: str = "dtype") -> None:
         super().__init__()
+        if activations not in ("dtype", "mxfp4"):
+            raise ValueError(f"mxfp4 moe: activations must be 'dtype' or 'mxfp4' (got {activations!r})")
         if not 1 <= top_k <= min(num_experts, 32):
             raise ValueError(f"mxfp4 moe needs 1 <= top_k <= min(num_experts, 32) (got top_k={top_k}, num_experts={num_experts})")
         self.hidden, self.intermediate, self.num_experts, self.top_k = hidden, intermediate, num_experts, top_k
         self.swiglu_limit, self.swiglu_alpha, self.dtype = float(swiglu_limit), float(swiglu_alpha), dtype
         self.router = nn.Linear(hidden, num_experts, bias=bias, device=device, dtype=dtype)
-        self.gate_up = MXFP4ExpertsLinearCuda(num_experts, hidden, 2 * intermediate, bias=bias, device=device, dtype=dtype)
-        self.down = MXFP4ExpertsLinearCuda(num_experts, intermediate, hidden, bias=bias, device=device, dtype=dtype)
+        self.activations = activations
+        experts = MXFP4A4ExpertsLinearCuda if activations == "mxfp4" else MXFP4ExpertsLinearCuda
+        self.gate_up = experts(num_experts, hidden, 2 * intermediate, bias=bias, device=device, dtype=dtype)
+        self.down = experts(num_experts, intermediate, hidden, bias=bias, device=device, dtype=dtype)
         self.register_buffer("expert_mask", None, persistent=False)
 
     def set_expert_mask(self, mask: torch.Tensor = None) -> None:

@@ -1,5 +1,6 @@
 // The MXFP4 format's device-side rules and the instruction wrappers shared by mxfp4.hip and mxfp4_moe.hip (gfx950): E8M0 scale codes to
-// fp32, the prefill forms' rebias, the fp4 -> fp16 / bf16 converts with their dot2 and MFMA, and the fp32 wave sum on the DPP network.
+// fp32, the prefill forms' rebias, the fp4 -> fp16 / bf16 converts with their dot2 and MFMA, the fp32 wave sum on the DPP network, and
+// the layout of the expert GEMMs' routing workspace.
 #pragma once
 #include "mfma_pipe.cuh"
 
@@ -45,6 +46,12 @@ __device__ __forceinline__ float wave_sum_f32(float v) {  // wave_sum_dpp's netw
     v = dpp_add<0x143, 0xc>(v);
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+
+// ---- the routing workspace of the grouped expert GEMMs (mxm_route_kernel of mxfp4_moe.hip writes it; mxfp4_moe.hip and mxfp4_moe_a4.hip read it)
+// int32: head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P]
+constexpr int MXM_BM = 128;      // rows of a row tile
+constexpr int MXM_MAX_E = 1024;  // bins of the routing kernel's scan
+constexpr int MXM_HEAD = 4;      // int32 words before the tile table: [0] the tile count
 
 // ---- prefill forms: four code bytes -> one 8-k MFMA fragment at the block's rebiased scale ---------------------------------------------
 template <int DT> struct mx_frag;

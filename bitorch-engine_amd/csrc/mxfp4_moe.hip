@@ -98,9 +98,7 @@ __global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restr
 }
 
 // ---- grouped prefill form: routing --------------------------------------------------------------------------------------------------------
-constexpr int MXM_BM = 128, MXM_BN = 128, MXM_BK = 64;
-constexpr int MXM_MAX_E = 1024;
-constexpr int MXM_HEAD = 4;  // int32 words before the tile table: [0] the tile count
+constexpr int MXM_BN = 128, MXM_BK = 64;  // MXM_BM, MXM_MAX_E and MXM_HEAD: mxfp4_common.cuh (the routing workspace's layout)
 
 // Workspace (int32): head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P].
 // max_tiles bounds sum_e ceil(count_e / BM) + ceil(skipped / BM): every tile holds a pair, and at most one tile per bin is not full.
@@ -341,6 +339,14 @@ size_t mxfp4_moe_workspace_bytes(long P, long E) {
     return (words * 4 + 15) / 16 * 16;
 }
 
+// The routing launch, shared with the W4A4 expert GEMM (mxfp4_moe_a4.hip): the workspace layout above, row tiles of MXM_BM = 128.
+long mxfp4_moe_max_tiles(long P, long E) { return mxm_max_tiles(P, E); }
+
+int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st) {
+    hipLaunchKernelGGL(mxm_route_kernel, dim3(1), dim3(1024), 0, st, idx, reinterpret_cast<int32_t*>(workspace), (int)P, (int)E, (int)mxm_max_tiles(P, E));
+    return check_launch("mxm_route_kernel");
+}
+
 int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                              void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
     const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
@@ -356,8 +362,7 @@ int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* q
     }
     int32_t* ws = reinterpret_cast<int32_t*>(workspace);
     const int max_tiles = (int)mxm_max_tiles(P, E);
-    hipLaunchKernelGGL(mxm_route_kernel, dim3(1), dim3(1024), 0, st, idx, ws, (int)P, (int)E, max_tiles);
-    int rc = check_launch("mxm_route_kernel");
+    int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
     if (rc) return rc;
     const dim3 grid((unsigned)(max_tiles * cdivl(N, MXM_BN)));
     if (dtype == BIE_F16)

@@ -1,0 +1,416 @@
+// MXFP4 W4A4 expert GEMM for gfx950: the stacked expert weights of mxfp4_moe.hip against activations quantised to MXFP4 on the fly,
+// contracted on the block-scaled matrix instructions (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A4 mixture-of-experts layer").  No
+// reference implementation exists.
+//
+//   T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p]; row(p) = p / S (x_per_pair = 0) or p
+//   xq / xs / row_flag: the stored rows of x (T or P of them) by the rule of mxa4_quantize_kernel (mxfp4_a4.hip)
+//   y[p, n] = dt( sum_b 2^(xs[row(p), b] + scales[e, n, b] - 254) * (sum_{k in b} e2m1(xq) * e2m1(qweight)) + bias[e, n] ),  e = idx[p]
+//   y[p, :] = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255; y[p, :] = +0 where idx[p] is outside [0, E), whatever
+//   the row's flag: the index is compared before any address is formed from it
+//
+// A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
+// row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
+//
+// Routed decode form (mxma4_decode_kernel, P <= 1024): a workgroup per pair and strip of 16 C16 columns of its expert, K split over the
+// 4 waves in 128-k steps as in mxa4_decode_kernel, on v_mfma_scale_f32_16x16x128_f8f6f4.  The pair's row is row 0 of the x operand,
+// rows 1 .. 15 are zero codes under scale code 127; the four partial sums meet in LDS.  FUSED (one launch, K <= MXMA4_ONE_K): the
+// workgroup quantises x_row(p) into LDS itself (a4_quantize_unit, the bits of mxa4_quantize_kernel; codes, scale bytes, and the
+// non-finite flag through the barrier) and reads neither xq nor a workspace.  Not FUSED: it reads xq / xs / row_flag from memory.
+// Grouped prefill form: mxa4_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
+// mxma4_gemm_kernel: mxa4_gemm_kernel's 128 x 128 tile, stage layout and operand placement on v_mfma_scale_f32_32x32x64_f8f6f4 (the
+// weight fragment is the A operand, the lane's scale in byte 0).  A row tile belongs to one expert, gathers the xq / xs rows of its
+// pairs through the pair list (whole 16-byte pieces of codes, whole scale bytes) and reads weights from (long)e * N; rows past the
+// segment enter as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the
+// skipped bin run no K loop and store zeros.  Workgroup -> tile walk per XCD as in mxm_gemm_kernel.
+#include "mxfp4_common.cuh"
+#include "mxfp4_a4_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// mxfp4_a4.hip, mxfp4_moe.hip
+int mxfp4_a4_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
+size_t mxfp4_moe_workspace_bytes(long P, long E);
+long mxfp4_moe_max_tiles(long P, long E);
+int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
+
+// ---- routed decode form -------------------------------------------------------------------------------------------------------------------
+// The largest K of the one-launch form: a row's image in LDS is K / 2 bytes of codes and K / 32 scale bytes (17408 bytes at the bound).
+constexpr int MXMA4_ONE_K = 32768;
+constexpr int MXMA4_DECODE_PAIRS = 1024;  // the grid's second dimension
+
+// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
+// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step.  xin is x (FUSED) or xq.
+template <int DT, int C16, bool FUSED>
+__global__ __launch_bounds__(256) void mxma4_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                           const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                           const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                           int N, int K, int x_per_pair) {
+    constexpr int C = 16 * C16;
+    __shared__ float red[4][C];
+    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MXMA4_ONE_K / 2 + MXMA4_ONE_K / 32 : 16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int p = blockIdx.y, n0 = blockIdx.x * C;
+    const int e = idx[p];
+    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
+        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
+        return;
+    }
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const long xrow = x_per_pair ? p : p / S;
+    const uint8_t* xqr = nullptr;
+    const uint8_t* xsr = nullptr;
+    int flagged;
+    if constexpr (FUSED) {
+        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
+        const int U = K >> 3;  // a multiple of 4: whole quads are in or out
+        int bad = 0;
+        for (int u = t; u < U; u += 256) {
+            uint32_t codes, scode;
+            a4_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
+            reinterpret_cast<uint32_t*>(img)[u] = codes;
+            if ((u & 3) == 0) img[(K >> 1) + (u >> 2)] = (unsigned char)scode;
+        }
+        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
+    } else {
+        xqr = reinterpret_cast<const uint8_t*>(xin) + xrow * (K >> 1);
+        xsr = xs + xrow * KB;
+        flagged = row_flag[xrow];
+    }
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+    const uint8_t* wrow[C16];
+    const uint8_t* srow[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) {
+        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
+        wrow[c] = qw + n * (K >> 1);
+        srow[c] = sc + n * KB;
+    }
+    mxa4_v4f acc[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t b[C16];
+        int sb[C16];
+#pragma unroll
+        for (int c = 0; c < C16; c++) {
+            b[c] = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow[c]) + kc);
+            sb[c] = __builtin_nontemporal_load(srow[c] + kc);
+        }
+        uint4_t a = uint4_t{0u, 0u, 0u, 0u};
+        int sa = 127;
+        if (r16 == 0 && kin) {
+            if constexpr (FUSED) {
+                a = *reinterpret_cast<const uint4_t*>(img + kb * 16);
+                sa = img[(K >> 1) + kb];
+            } else {
+                a = reinterpret_cast<const uint4_t*>(xqr)[kb];
+                sa = xsr[kb];
+            }
+        }
+        if (!kin) {
+#pragma unroll
+            for (int c = 0; c < C16; c++) {
+                b[c] = uint4_t{0u, 0u, 0u, 0u};
+                sb[c] = 127;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C16; c++) acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(a), a4_frag(b[c]), acc[c], 4, 4, 0, sa, 0, sb[c]);
+    }
+    // C/D: column n = lane & 15, row m = 4 (lane >> 4) + r: the pair's row is register 0 of lanes 0 .. 15
+    if (lane < 16) {
+#pragma unroll
+        for (int c = 0; c < C16; c++) red[wave][c * 16 + lane] = acc[c][0];
+    }
+    __syncthreads();
+    if (t < C) {
+        const int n = n0 + t;
+        if (n < N) {
+            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
+            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
+            dt_traits<DT>::store(y, (long)p * N + n, v);
+        }
+    }
+}
+
+// ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
+constexpr int MXMA4_BN = 128, MXMA4_BK = 128;          // k per stage: 64 code bytes and 4 scale bytes per row
+constexpr int MXMA4_PITCH = MXMA4_BK / 2 + 16;         // as A4_PITCH of mxfp4_a4.hip
+constexpr int MXMA4_ROWS = MXM_BM + MXMA4_BN;          // rows of the stage image: 0 .. MXM_BM - 1 = x, the rest = weights
+constexpr int MXMA4_NLD = MXMA4_ROWS * 4 / 256;        // 16-byte pieces per thread and stage: row = piece / 4, quarter = piece % 4
+constexpr int MXMA4_STAGE = MXMA4_ROWS * MXMA4_PITCH + MXMA4_ROWS * 4;
+static_assert(MXMA4_ROWS == 256, "one scale dword per thread and stage");
+
+// 4 waves as 2 x 2, wave tile 64 x 64 (mxa4_gemm_kernel with WM = WN = 2).  Workgroup -> (row tile, column tile): the workgroups of one
+// XCD (blockIdx.x & 7) walk the row tiles of one column tile after another, so the tiles of one expert, which follow each other in the
+// table, find the expert's 128 columns of weights in that XCD's L2.
+template <int DT>
+__global__ __launch_bounds__(256) void mxma4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                         const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                         const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                         int N, int K, int x_per_pair, int max_tiles) {
+    constexpr int BM = MXM_BM, WM = 2, WN = 2;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MXMA4_STAGE];
+    __shared__ int prow[BM];  // the tile's pairs, -1 past the segment
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    int bid = blockIdx.x;
+    {
+        const int nblk = gridDim.x, xcd = bid & 7, per = nblk >> 3, rem = nblk & 7;
+        bid = xcd * per + (xcd < rem ? xcd : rem) + (bid >> 3);
+    }
+    const int tile_m = bid % max_tiles, tile_n = bid / max_tiles;
+    if (tile_m >= ws[0]) return;  // a surplus workgroup (uniform)
+    const int e = ws[MXM_HEAD + tile_m], first = ws[MXM_HEAD + max_tiles + tile_m], rows = ws[MXM_HEAD + 2 * max_tiles + tile_m];
+    const int32_t* list = ws + MXM_HEAD + 3 * (long)max_tiles;
+    if (t < BM) prow[t] = t < rows ? list[first + t] : -1;
+    __syncthreads();
+    const int n0 = tile_n * MXMA4_BN;
+    if (e >= E) {  // the skipped bin: zero rows
+        for (int i = t; i < BM * MXMA4_BN; i += 256) {
+            const int p = prow[i / MXMA4_BN], n = n0 + i % MXMA4_BN;
+            if (p >= 0 && n < N) dt_traits<DT>::store(y, (long)p * N + n, 0.0f);
+        }
+        return;
+    }
+    const int KB = K >> 5, KT = (K + MXMA4_BK - 1) / MXMA4_BK;
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+
+    // load slots: pieces t, t + 256, ... of the stage image; thread t also loads row t's four scale bytes
+    const uint8_t* csrc[MXMA4_NLD];
+    bool cok[MXMA4_NLD];
+#pragma unroll
+    for (int i = 0; i < MXMA4_NLD; i++) {
+        const int row = (t + 256 * i) >> 2;
+        if (row < BM) {
+            const int p = prow[row];
+            cok[i] = p >= 0;
+            csrc[i] = xq + (long)(p < 0 ? 0 : x_per_pair ? p : p / S) * (K >> 1);
+        } else {
+            cok[i] = n0 + row - BM < N;
+            csrc[i] = qw + (r0 + min(n0 + row - BM, N - 1)) * (K >> 1);
+        }
+    }
+    bool sok;
+    const uint8_t* ssrc;
+    if (t < BM) {
+        const int p = prow[t];
+        sok = p >= 0;
+        ssrc = xs + (long)(p < 0 ? 0 : x_per_pair ? p : p / S) * KB;
+    } else {
+        sok = n0 + t - BM < N;
+        ssrc = sc + (r0 + min(n0 + t - BM, N - 1)) * KB;
+    }
+    uint4_t rc[MXMA4_NLD];
+    uint32_t rs = 0x7f7f7f7fu;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < MXMA4_NLD; i++) {
+            const int kb = kt * 4 + ((t + 256 * i) & 3);
+            rc[i] = (cok[i] && kb < KB) ? *reinterpret_cast<const uint4_t*>(csrc[i] + (long)kb * 16) : uint4_t{0u, 0u, 0u, 0u};
+        }
+        rs = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int kb = kt * 4 + j;
+            const uint32_t s = (sok && kb < KB) ? (uint32_t)ssrc[kb] : 127u;
+            rs |= s << (8 * j);
+        }
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MXMA4_STAGE;
+#pragma unroll
+        for (int i = 0; i < MXMA4_NLD; i++) {
+            const int q = t + 256 * i;
+            *reinterpret_cast<uint4_t*>(st + (q >> 2) * MXMA4_PITCH + (q & 3) * 16) = rc[i];
+        }
+        reinterpret_cast<uint32_t*>(st + MXMA4_ROWS * MXMA4_PITCH)[t] = rs;
+    };
+
+    float16_t acc[WN][WM];  // [weight row block j][x row block i]: D rows = columns n of y, D columns = rows of the tile
+#pragma unroll
+    for (int j = 0; j < WN; j++)
+#pragma unroll
+        for (int i = 0; i < WM; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[j][i][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * MXMA4_STAGE;
+        const uint32_t* ss = reinterpret_cast<const uint32_t*>(st + MXMA4_ROWS * MXMA4_PITCH);
+        uint32_t sxa[WM], swa[WN];  // the row's four scale bytes, shifted so that this lane's block of k-step ks sits in byte 2 ks
+#pragma unroll
+        for (int i = 0; i < WM; i++) sxa[i] = ss[wy * 32 * WM + i * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int j = 0; j < WN; j++) swa[j] = ss[BM + wx * 32 * WN + j * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            mxa4_v8i fx[WM], fw[WN];
+#pragma unroll
+            for (int i = 0; i < WM; i++)
+                fx[i] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (wy * 32 * WM + i * 32 + rl) * MXMA4_PITCH + (ks * 2 + hh) * 16));
+#pragma unroll
+            for (int j = 0; j < WN; j++)
+                fw[j] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (BM + wx * 32 * WN + j * 32 + rl) * MXMA4_PITCH + (ks * 2 + hh) * 16));
+#pragma unroll
+            for (int j = 0; j < WN; j++)
+#pragma unroll
+                for (int i = 0; i < WM; i++)
+                    acc[j][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[j], fx[i], acc[j][i], 4, 4, 0, (int)((swa[j] >> (16 * ks)) & 0xffu), 0,
+                                                                                (int)((sxa[i] >> (16 * ks)) & 0xffu));
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: D column (= tile row) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh: registers 4q .. 4q + 3 are four
+    // consecutive n of one pair -> one 8-byte store where N allows it; row r of the tile goes to y[pair r]
+    const bool vec = (N & 3) == 0;
+#pragma unroll
+    for (int i = 0; i < WM; i++) {
+        const int p = prow[wy * 32 * WM + i * 32 + rl];
+        if (p < 0) continue;
+        const bool rbad = row_flag[x_per_pair ? p : p / S] != 0;
+#pragma unroll
+        for (int j = 0; j < WN; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int n = n0 + wx * 32 * WN + j * 32 + 8 * q + 4 * hh;
+                if (n >= N) continue;
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    v[r] = acc[j][i][4 * q + r];
+                    if (n + r < N) {
+                        if (rbad || ecol[r0 + n + r] == 255u) v[r] = a4_nan();
+                        if (bias) v[r] += dt_traits<DT>::load(bias, r0 + n + r);
+                    }
+                }
+                if (vec) {
+                    uint16_t h[4];
+                    dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
+                    dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
+                    uint2_t o;
+                    o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+                    o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+                    *reinterpret_cast<uint2_t*>(reinterpret_cast<uint16_t*>(y) + (long)p * N + n) = o;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (n + r < N) dt_traits<DT>::store(y, (long)p * N + n + r, v[r]);
+                }
+            }
+    }
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The routed decode form exists for P <= MXMA4_DECODE_PAIRS.  The plan's bound was measured (tools/mxfp4_moe_a4_bench.py,
+// profiles/mxfp4_moe_a4_bench.jsonl, the `sweep` rows: both gpt-oss-20b projections at E = 32 and E = 128, fp16 and bf16, both forms
+// forced at P = 1, 2, 4, ..., 1024, graph time, routings and weight stacks rotated; fp16 and bf16 agree within 1 %).  The decode form
+// streams an expert's weights once per pair and grows linearly in P (9.4 / 16.8 / 51 / 96 / 184 / 363 us at P = 1 / 4 / 16 / 32 / 64 /
+// 128 on 2880 -> 5760); the grouped form costs 37 us at P = 1 (three launches, one row tile walking K) and then grows with the number
+// of experts that hold a pair.  At E = 32 the decode form led at every P <= 32 (P = 32: 96 against 134 us at 5760, 51 against 70 at
+// 2880) and the grouped form from P = 64 on (184 against 139, 95 against 69; 723 against 145 at P = 256).  At E = 128, where nearly
+// every pair of a small call has an expert of its own, the decode form still led at P = 64 (186 against 231 - 250 us, 97 against 131);
+// P = 128 was a tie either way (367 against 345 - 352 at 5760, 187 against 196 at 2880) and the grouped form led from P = 256 on (734
+// against 452, 371 against 261).  So the plan takes the decode form for P <= 32, and up to P = 64 while P <= E / 2.  E between 32 and
+// 128 and beyond 128 was not measured: the second clause extends the E = 128 rows by the pairs-per-expert argument.  (The rows' `plan`
+// column is the plan of the build that measured them, the weight-only plan's 64 / 256 / 2 E, which these rows replaced.)
+// The strip width of the decode form: 16, 32 and 64 columns per workgroup measured at P = 1, 4, 16, 64 on both projections (the `strip`
+// rows): 16 columns were ahead or level on every row (P = 1: 8.9 / 9.3 / 12.3 us at 5760; P = 64: 174 / 183 / 199), so the wider
+// strips' saving of the per-workgroup quantisation does not pay for their fewer workgroups.
+constexpr int MXMA4_PLAN_PAIRS = 32, MXMA4_PLAN_PAIRS_SPARSE = 64;
+constexpr int MXMA4_STRIP = 1;  // C16 of the decode form: strips of 16 columns (BIE_MXFP4_MOE_A4_STRIP = 1 / 2 / 4 under BIE_TUNING)
+
+bool mxfp4_moe_a4_decode_ok(long P) { return P >= 1 && P <= MXMA4_DECODE_PAIRS; }
+bool mxfp4_moe_a4_one_launch_ok(long K) { return K <= MXMA4_ONE_K; }
+
+int mxfp4_moe_a4_form(long P, long E, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_MOE_A4_FORM", -1);
+    if (f == 0 && P <= MXMA4_DECODE_PAIRS) return 0;
+    if (f == 1) return 1;
+    return (P <= MXMA4_PLAN_PAIRS || (P <= MXMA4_PLAN_PAIRS_SPARSE && 2 * P <= E)) ? 0 : 1;
+}
+
+// Workspace of bie_mxfp4_moe_a4_forward, every region 16-byte aligned: xq [R, K/2], xs [R, K/32], row_flag [R] for the R stored rows of
+// x (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip.
+static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
+static long a4m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
+static size_t a4m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)(K / 2)); }
+static size_t a4m_flag_offset(long R, long K) { return a4m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
+static size_t a4m_route_offset(long R, long K) { return a4m_flag_offset(R, K) + al16((size_t)R); }
+
+size_t mxfp4_moe_a4_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    return a4m_route_offset(a4m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+}
+
+template <int DT, int C16, bool FUSED>
+static void a4m_decode_launch_t(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                                const uint8_t* ecol, const void* bias, void* y, long P, int S, int E, int N, int K, int xpp, hipStream_t st) {
+    const dim3 grid((unsigned)cdivl(N, 16 * C16), (unsigned)P);
+    hipLaunchKernelGGL((mxma4_decode_kernel<DT, C16, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, S, E, N, K, xpp);
+}
+
+template <int DT, bool FUSED>
+static int a4m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
+    const int strip = BIE_KNOB("BIE_MXFP4_MOE_A4_STRIP", MXMA4_STRIP);
+    if (strip >= 4) a4m_decode_launch_t<DT, 4, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else if (strip >= 2) a4m_decode_launch_t<DT, 2, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else a4m_decode_launch_t<DT, 1, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    return check_launch("mxma4_decode_kernel");
+}
+
+// The contraction from quantised activations.  form 0: the routed kernel reading xq from memory (no workspace); form 1: routing into the
+// workspace (the routing region alone), then the grouped GEMM.
+int mxfp4_moe_a4_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st) {
+    const long P = T * S;
+    if (form == 0) {
+        if (dtype == BIE_F16) return a4m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a4m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
+    if (rc) return rc;
+    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
+    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, MXMA4_BN)));
+    if (dtype == BIE_F16)
+        hipLaunchKernelGGL(mxma4_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    else
+        hipLaunchKernelGGL(mxma4_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    return check_launch("mxma4_gemm_kernel");
+}
+
+// The whole layer from x.  form 0 with K <= MXMA4_ONE_K: one launch, the workspace is not touched.
+int mxfp4_moe_a4_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
+    const long P = T * S, R = a4m_rows(T, S, x_per_pair);
+    if (form == 0 && K <= MXMA4_ONE_K) {
+        if (dtype == BIE_F16) return a4m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a4m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a4m_xs_offset(R, K);
+    uint8_t* rf = xq + a4m_flag_offset(R, K);
+    const int rc = mxfp4_a4_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_moe_a4_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a4m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+}
+
+}  // namespace bie
