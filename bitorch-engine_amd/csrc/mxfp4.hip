@@ -11,11 +11,11 @@
 // into two exact 16-bit values (scale 1.0), v_dot2_f32_{bf16,f16} sums 16 products per row into fp32, and that partial is multiplied by
 // the block's fp32 scale (a power of two: exact).  No 16-bit image of W exists, so the fp16 form has the fp32 range of W.  The K-split
 // partials are summed on the DPP network, then across the 4 waves in LDS.
-// Prefill form (mx_gemm_kernel): a 128 x 128 tile GEMM on v_mfma_f32_32x32x16_{bf16,f16}, double-buffered LDS.  The weight tile is
-// staged PACKED (32 bytes per row and 64-k stage, plus two scale words) and converted to B fragments after the LDS read: a lane's 8-k
-// fragment is 4 code bytes = 4 converts.  Each column is rebiased by its largest scale code e_col[n] (bie_mxfp4_col_exp, computed once
-// at load time): fragments hold e2m1 * 2^(s - e_col[n]) <= 6 and the fp32 epilogue multiplies by 2^(e_col[n] - 127).  A column with a
-// scale-255 block has e_col = 255, which makes the whole column NaN in the epilogue.
+// Prefill form (mx_gemm_kernel): mx_gemm_tile of mxfp4_common.cuh, a 128 x 128 tile GEMM on v_mfma_f32_32x32x16_{bf16,f16} with
+// double-buffered LDS, on the rows m0 .. of x.  The weight tile is staged PACKED (32 bytes per row and 64-k stage, plus two scale
+// words) and converted to B fragments after the LDS read.  Each column is rebiased by its largest scale code e_col[n]
+// (bie_mxfp4_col_exp, computed once at load time): fragments hold e2m1 * 2^(s - e_col[n]) <= 6 and the fp32 epilogue multiplies by
+// 2^(e_col[n] - 127).  A column with a scale-255 block has e_col = 255, which makes the whole column NaN in the epilogue.
 #include "mxfp4_common.cuh"
 
 #pragma clang fp contract(off)
@@ -32,14 +32,7 @@ __device__ __forceinline__ float mx_e2m1(uint32_t c) {  // the code's value as f
 template <int DT>
 __device__ __forceinline__ float mx_load(const void* p, long i) { return dt_traits<DT>::load(p, i); }
 
-// |a| -> E2M1 magnitude index, round to nearest, ties to the even index (0.25 -> 0, 0.75 -> 2, 1.25 -> 2, 1.75 -> 4, 2.5 -> 4, 3.5 -> 6,
-// 5 -> 6), saturating at 6
-__device__ __forceinline__ uint32_t mx_round_e2m1(float a) {
-    return a <= 0.25f ? 0u : a < 0.75f ? 1u : a <= 1.25f ? 2u : a < 1.75f ? 3u : a <= 2.5f ? 4u : a < 3.5f ? 5u : a <= 5.0f ? 6u : 7u;
-}
-
-// One thread per 32-value block: amax, e = floor(log2 amax) - 2 clamped to [-127, 127] (from the fp32 exponent bits, subnormal amax by
-// its leading bit), codes of w * 2^-e (exact: a power-of-two multiply of a normal result).  An all-zero block: scale 0, codes 0.
+// One thread per 32-value block: amax, the block's scale 2^e (mx_block_scale), codes of w * 2^-e.  An all-zero block: scale 0, codes 0.
 template <int DT>
 __global__ __launch_bounds__(256) void mx_quantize_kernel(const void* __restrict__ w, uint8_t* __restrict__ qw, uint8_t* __restrict__ sc, long nblk) {
     const long b = (long)blockIdx.x * 256 + threadIdx.x;
@@ -54,12 +47,8 @@ __global__ __launch_bounds__(256) void mx_quantize_kernel(const void* __restrict
     uint4_t codes = {0u, 0u, 0u, 0u};
     uint32_t scode = 0u;
     if (amax > 0.0f) {
-        const uint32_t bits = __float_as_uint(amax);
-        const int ex = (int)(bits >> 23);
-        const int fl = ex ? ex - 127 : (31 - __builtin_clz(bits & 0x7fffffu)) - 149;  // floor(log2(amax))
-        const int e = min(max(fl - 2, -127), 127);
-        scode = (uint32_t)(e + 127);
-        const float inv = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e, normal: e <= 125 for any finite amax
+        float inv;
+        scode = mx_block_scale(amax, inv);
 #pragma unroll
         for (int i = 0; i < 32; i++) {
             const uint32_t c = mx_round_e2m1(fabsf(v[i] * inv)) | ((__float_as_uint(v[i]) >> 28) & 8u);
@@ -127,12 +116,7 @@ __global__ __launch_bounds__(256) void mx_decode_kernel(const uint16_t* __restri
         }
         typename P::t wv[C][8];
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-            wv[c][0] = P::template cvt<0>(wb[c].x); wv[c][1] = P::template cvt<1>(wb[c].x);
-            wv[c][2] = P::template cvt<2>(wb[c].x); wv[c][3] = P::template cvt<3>(wb[c].x);
-            wv[c][4] = P::template cvt<0>(wb[c].y); wv[c][5] = P::template cvt<1>(wb[c].y);
-            wv[c][6] = P::template cvt<2>(wb[c].y); wv[c][7] = P::template cvt<3>(wb[c].y);
-        }
+        for (int c = 0; c < C; c++) mx_unpack16<DT>(wb[c], wv[c]);
         float s[C];
 #pragma unroll
         for (int c = 0; c < C; c++) s[c] = e8m0_f32(sb[c]);
@@ -173,114 +157,14 @@ __global__ __launch_bounds__(256) void mx_decode_kernel(const uint16_t* __restri
 }
 
 // ---- prefill form -------------------------------------------------------------------------------------------------------------------
-constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 64;
-constexpr int MX_APITCH = MX_BK * 2 + 16;  // bytes per x row in LDS (16-byte pad: the fragment reads of 32 rows spread over the banks)
-constexpr int MX_BPITCH = 36;              // bytes per weight row: 32 code bytes + 4 (9 dwords, the 32 rows of a read on distinct banks)
-constexpr int MX_STAGE = MX_BM * MX_APITCH + MX_BN * MX_BPITCH + MX_BN * 2 * 4;  // x, codes, the two fp32 rebiased scales per row
-
-// 4 waves as 2 x 2, wave tile 64 x 64 (2 x 2 MFMA tiles).  Per 64-k stage a thread loads 4 x 16 bytes of x, 16 code bytes and one
-// scale byte into registers while the MFMAs run on the other LDS buffer, then writes them (the scale already rebiased to fp32).
-// Past M / N / K: x and codes load as zero, scales as 1.0, so the padding adds exact zeros.
+// A workgroup per 128 x 128 tile (mx_gemm_tile), the tiles walked in pipe_tile's order.
 template <int DT>
 __global__ __launch_bounds__(256) void mx_gemm_kernel(const uint16_t* __restrict__ x, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
                                                       const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int M, int N,
                                                       int K, int tiles_n) {
-    typedef mx_frag<DT> F;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX_STAGE];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
     int tile_m, tile_n;
     pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
-    const int m0 = tile_m * MX_BM, n0 = tile_n * MX_BN;
-    const int KT = (K + MX_BK - 1) / MX_BK, KB = K >> 5;
-
-    // this thread's load slots
-    const int bn = t >> 1, bh = t & 1;  // weight row bn of the tile, 16-byte half bh; scale block bh of the stage
-    const int nb = n0 + bn;
-    const bool nb_ok = nb < N;
-    const uint8_t* wsrc = qw + (long)min(nb, N - 1) * (K >> 1) + bh * 16;
-    const uint8_t* ssrc = sc + (long)min(nb, N - 1) * KB + bh;
-    const uint32_t e = nb_ok ? ecol[nb] : 0u;
-    uint4_t ra[4], rb;
-    float rs;
-    auto load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int q = t + 256 * i, row = q >> 3, c16 = q & 7, m = m0 + row, k = kt * MX_BK + c16 * 8;
-            ra[i] = (m < M && k < K) ? *reinterpret_cast<const uint4_t*>(x + (long)m * K + k) : uint4_t{0u, 0u, 0u, 0u};
-        }
-        const bool kin = kt * MX_BK + bh * 32 < K;
-        rb = (nb_ok && kin) ? __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wsrc + kt * 32)) : uint4_t{0u, 0u, 0u, 0u};
-        rs = (nb_ok && kin) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), e) : 1.0f;
-    };
-    auto store = [&](int buf) {
-        unsigned char* st = lds + buf * MX_STAGE;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
-            *reinterpret_cast<uint4_t*>(st + row * MX_APITCH + c16 * 16) = ra[i];
-        }
-        uint32_t* wb = reinterpret_cast<uint32_t*>(st + MX_BM * MX_APITCH + bn * MX_BPITCH + bh * 16);
-        wb[0] = rb.x; wb[1] = rb.y; wb[2] = rb.z; wb[3] = rb.w;
-        reinterpret_cast<float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH)[bn * 2 + bh] = rs;
-    };
-
-    float16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
-
-    const int rl = lane & 31, hh = lane >> 5;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < KT; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < KT) load(kt + 1);
-        const unsigned char* st = lds + buf * MX_STAGE;
-        const float* ss = reinterpret_cast<const float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH);
-#pragma unroll
-        for (int ks = 0; ks < MX_BK / 16; ks++) {
-            typename F::t a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX_APITCH + ks * 32 + hh * 16));
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int n = wx * 64 + j * 32 + rl;
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(st + MX_BM * MX_APITCH + n * MX_BPITCH + ks * 8 + hh * 4);
-                b[j] = F::cvt(w, ss[n * 2 + (ks >> 1)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
-        }
-        if (kt + 1 < KT) store(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D: column n = lane & 31, row m = (r & 3) + 8 (r >> 2) + 4 hh
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int n = n0 + wx * 64 + j * 32 + rl;
-        if (n >= N) continue;
-        const float cs = e8m0_f32(ecol[n]);
-        const float bv = bias ? dt_traits<DT>::load(bias, n) : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                if (m < M) {
-                    float v = acc[i][j][r] * cs;
-                    if (bias) v += bv;
-                    dt_traits<DT>::store(y, (long)m * N + n, v);
-                }
-            }
-    }
+    mx_gemm_tile<DT>(mx_rows_dense{tile_m * MX_BM, M}, x, qw, sc, ecol, bias, y, 0L, tile_n * MX_BN, N, K);
 }
 
 // ---- plan and launchers -----------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // MXFP4 W4A4 linear layer for gfx950: the MXFP4 weights of mxfp4.hip against activations quantised to MXFP4 on the fly, contracted on the
 // block-scaled matrix instructions with REAL block scales (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A4 linear layer").
 //
-//   xq uint8 [M, K/2], xs uint8 [M, K/32]: x quantised per row and block of 32 by the OCP MX v1.0 rule of mx_quantize_kernel (mxfp4.hip)
+//   xq uint8 [M, K/2], xs uint8 [M, K/32]: x quantised per row and block of 32 by the OCP MX v1.0 rule of the weight quantiser (mxfp4_common.cuh)
 //   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (its codes are unspecified), else 0
 //   y[m, n] = dt( sum_b 2^(xs[m, b] + scales[n, b] - 254) * (sum_{k in b} e2m1(xq) * e2m1(qweight)) + bias[n] )
 //   y[m, :] = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255 (a weight block with scale code 255)
@@ -17,9 +17,8 @@
 // Decode form (mxa4_decode_kernel, M <= 64): a workgroup per 16 output columns, K split over its 4 waves; every wave loads its B
 // fragments straight from qweight (non-temporal, 16 bytes per lane) and the x fragments from xq (cache-resident), one
 // 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS.
-// Prefill form (mxa4_gemm_kernel): a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2, packed codes and scale bytes staged
-// through registers into double-buffered LDS (128 k per stage); per 64 k a wave reads WM + WN fragments and as many scale bytes and
-// issues WM * WN MFMAs.  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one row of y.
+// Prefill form (mxa4_gemm_kernel): mxa4_gemm_tile of mxfp4_a4_common.cuh, a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2,
+// packed codes and scale bytes staged through registers into double-buffered LDS (128 k per stage), on the rows m0 .. of xq / xs.
 #include "mxfp4_a4_common.cuh"
 
 #pragma clang fp contract(off)
@@ -122,159 +121,14 @@ __global__ __launch_bounds__(256) void mxa4_decode_kernel(const uint8_t* __restr
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------
-constexpr int A4_BK = 128;                    // k per stage: 64 code bytes and 4 scale bytes per row
-constexpr int A4_PITCH = A4_BK / 2 + 16;      // 80 bytes per row in LDS: the 16-byte fragment reads of 16 rows fall on distinct banks
-
-// Tile (64 WM rows of x) x (64 WN columns).  LDS stage: x codes [64 WM][80], weight codes [64 WN][80], x scales [64 WM] dwords, weight
-// scales [64 WN] dwords (byte j of a row's dword = the scale of the stage's block j).  Past M / N / K: zero codes under scale 2^0.
+// A workgroup per (64 WM) x (64 WN) tile (mxa4_gemm_tile), the tiles walked in pipe_tile's order.
 template <int DT, int WM, int WN>
 __global__ __launch_bounds__(256) void mxa4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                         const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                         const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
-    constexpr int BM = 64 * WM, BN = 64 * WN, ROWS = BM + BN;
-    constexpr int NLD = ROWS * 4 / 256;  // 16-byte pieces per thread and stage: row = piece / 4, quarter = piece % 4
-    constexpr int STAGE = ROWS * A4_PITCH + ROWS * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
     int tile_m, tile_n;
     pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int KB = K >> 5, KT = (K + A4_BK - 1) / A4_BK;
-
-    // load slots: pieces t, t + 256, ... of the stage image (rows 0 .. BM - 1 = x, BM .. = weights); thread t < ROWS also loads row t's scales
-    const uint8_t* csrc[NLD];
-    bool cok[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; i++) {
-        const int p = t + 256 * i, row = p >> 2;
-        if (row < BM) {
-            cok[i] = m0 + row < M;
-            csrc[i] = xq + (long)min(m0 + row, M - 1) * (K >> 1);
-        } else {
-            cok[i] = n0 + row - BM < N;
-            csrc[i] = qw + (long)min(n0 + row - BM, N - 1) * (K >> 1);
-        }
-    }
-    const bool s_thread = t < ROWS;
-    bool sok = false;
-    const uint8_t* ssrc = xs;
-    if (s_thread) {
-        if (t < BM) {
-            sok = m0 + t < M;
-            ssrc = xs + (long)min(m0 + t, M - 1) * KB;
-        } else {
-            sok = n0 + t - BM < N;
-            ssrc = sc + (long)min(n0 + t - BM, N - 1) * KB;
-        }
-    }
-    uint4_t rc[NLD];
-    uint32_t rs = 0x7f7f7f7fu;
-    auto load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int kb = kt * 4 + ((t + 256 * i) & 3);
-            rc[i] = (cok[i] && kb < KB) ? *reinterpret_cast<const uint4_t*>(csrc[i] + (long)kb * 16) : uint4_t{0u, 0u, 0u, 0u};
-        }
-        if (s_thread) {
-            rs = 0u;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int kb = kt * 4 + j;
-                const uint32_t s = (sok && kb < KB) ? (uint32_t)ssrc[kb] : 127u;
-                rs |= s << (8 * j);
-            }
-        }
-    };
-    auto store = [&](int buf) {
-        unsigned char* st = lds + buf * STAGE;
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int p = t + 256 * i;
-            *reinterpret_cast<uint4_t*>(st + (p >> 2) * A4_PITCH + (p & 3) * 16) = rc[i];
-        }
-        if (s_thread) reinterpret_cast<uint32_t*>(st + ROWS * A4_PITCH)[t] = rs;
-    };
-
-    float16_t acc[WN][WM];  // [weight row block j][x row block i]: D rows = columns n of y, D columns = rows m of y
-#pragma unroll
-    for (int j = 0; j < WN; j++)
-#pragma unroll
-        for (int i = 0; i < WM; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[j][i][r] = 0.0f;
-
-    const int rl = lane & 31, hh = lane >> 5;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < KT; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < KT) load(kt + 1);
-        const unsigned char* st = lds + buf * STAGE;
-        const uint32_t* ss = reinterpret_cast<const uint32_t*>(st + ROWS * A4_PITCH);
-        uint32_t sxa[WM], swa[WN];  // the row's four scale bytes, shifted so that this lane's block of k-step ks sits in byte 2 ks
-#pragma unroll
-        for (int i = 0; i < WM; i++) sxa[i] = ss[wy * 32 * WM + i * 32 + rl] >> (8 * hh);
-#pragma unroll
-        for (int j = 0; j < WN; j++) swa[j] = ss[BM + wx * 32 * WN + j * 32 + rl] >> (8 * hh);
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            mxa4_v8i fx[WM], fw[WN];
-#pragma unroll
-            for (int i = 0; i < WM; i++)
-                fx[i] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (wy * 32 * WM + i * 32 + rl) * A4_PITCH + (ks * 2 + hh) * 16));
-#pragma unroll
-            for (int j = 0; j < WN; j++)
-                fw[j] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (BM + wx * 32 * WN + j * 32 + rl) * A4_PITCH + (ks * 2 + hh) * 16));
-#pragma unroll
-            for (int j = 0; j < WN; j++)
-#pragma unroll
-                for (int i = 0; i < WM; i++)
-                    acc[j][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[j], fx[i], acc[j][i], 4, 4, 0, (int)((swa[j] >> (16 * ks)) & 0xffu), 0,
-                                                                                (int)((sxa[i] >> (16 * ks)) & 0xffu));
-        }
-        if (kt + 1 < KT) store(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D: D column (= row m of y) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh: registers 4q .. 4q + 3 are four
-    // consecutive n of one m -> one 8-byte store where N allows it
-    const bool vec = (N & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < WM; i++) {
-        const int m = m0 + wy * 32 * WM + i * 32 + rl;
-        if (m >= M) continue;
-        const bool rbad = row_flag[m] != 0;
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int n = n0 + wx * 32 * WN + j * 32 + 8 * q + 4 * hh;
-                if (n >= N) continue;
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    v[r] = acc[j][i][4 * q + r];
-                    if (n + r < N) {
-                        if (rbad || ecol[n + r] == 255u) v[r] = a4_nan();
-                        if (bias) v[r] += dt_traits<DT>::load(bias, n + r);
-                    }
-                }
-                if (vec) {
-                    uint16_t h[4];
-                    dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
-                    dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
-                    uint2_t o;
-                    o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-                    o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-                    *reinterpret_cast<uint2_t*>(reinterpret_cast<uint16_t*>(y) + (long)m * N + n) = o;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        if (n + r < N) dt_traits<DT>::store(y, (long)m * N + n + r, v[r]);
-                }
-            }
-    }
+    mxa4_gemm_tile<DT, WM, WN>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// The MXFP4 format's device-side rules and the instruction wrappers shared by mxfp4.hip and mxfp4_moe.hip (gfx950): E8M0 scale codes to
-// fp32, the prefill forms' rebias, the fp4 -> fp16 / bf16 converts with their dot2 and MFMA, the fp32 wave sum on the DPP network, and
-// the layout of the expert GEMMs' routing workspace.
+// The MXFP4 format's device-side rules and everything the MXFP4 translation units share (gfx950): E8M0 scale codes to fp32, the
+// quantiser's rounding and block-scale rules, the fp4 -> fp16 / bf16 converts with their dot2 and MFMA, the fp32 wave sum on the DPP
+// network, the row sources of the tile GEMMs, the weight-only 128 x 128 tile body (mx_gemm_tile: mx_gemm_kernel of mxfp4.hip and
+// mxm_gemm_kernel of mxfp4_moe.hip), and the routing workspace of the grouped expert GEMMs with their common prologue (mxm_tile_begin).
 #pragma once
 #include "mfma_pipe.cuh"
 
@@ -18,6 +19,24 @@ __device__ __forceinline__ float mx_rebias(uint32_t s, uint32_t e) {
     return __uint_as_float(d < -126 ? 0u : (uint32_t)(d + 127) << 23);
 }
 
+// |a| -> E2M1 magnitude index, round to nearest, ties to the even index (0.25 -> 0, 0.75 -> 2, 1.25 -> 2, 1.75 -> 4, 2.5 -> 4, 3.5 -> 6,
+// 5 -> 6), saturating at 6
+__device__ __forceinline__ uint32_t mx_round_e2m1(float a) {
+    return a <= 0.25f ? 0u : a < 0.75f ? 1u : a <= 1.25f ? 2u : a < 1.75f ? 3u : a <= 2.5f ? 4u : a < 3.5f ? 5u : a <= 5.0f ? 6u : 7u;
+}
+
+// A block's scale from its largest magnitude amax > 0: e = floor(log2 amax) - 2 clamped to [-127, 127] (from the fp32 exponent bits,
+// a subnormal amax by its leading bit).  Returns the E8M0 code e + 127 and sets inv = 2^-e (normal: e <= 125 for any finite amax), so
+// that w * inv is exact: a power-of-two multiply of a normal result.
+__device__ __forceinline__ uint32_t mx_block_scale(float amax, float& inv) {
+    const uint32_t bits = __float_as_uint(amax);
+    const int ex = (int)(bits >> 23);
+    const int fl = ex ? ex - 127 : (31 - __builtin_clz(bits & 0x7fffffu)) - 149;  // floor(log2(amax))
+    const int e = min(max(fl - 2, -127), 127);
+    inv = __uint_as_float((uint32_t)(127 - e) << 23);
+    return (uint32_t)(e + 127);
+}
+
 // ---- decode forms: two codes -> two exact 16-bit values (scale 1.0), dot2 into fp32 -----------------------------------------------------
 template <int DT> struct mx_pair;
 template <> struct mx_pair<BIE_BF16> {
@@ -33,6 +52,16 @@ template <> struct mx_pair<BIE_F16> {
     static __device__ __forceinline__ float dot(t a, uint32_t b, float c) { return __builtin_amdgcn_fdot2(a, __builtin_bit_cast(t, b), c, false); }
 };
 
+// 16 codes (two dwords) -> eight pairs of exact 16-bit values
+template <int DT>
+__device__ __forceinline__ void mx_unpack16(const uint2_t& w, typename mx_pair<DT>::t (&v)[8]) {
+    typedef mx_pair<DT> P;
+    v[0] = P::template cvt<0>(w.x); v[1] = P::template cvt<1>(w.x);
+    v[2] = P::template cvt<2>(w.x); v[3] = P::template cvt<3>(w.x);
+    v[4] = P::template cvt<0>(w.y); v[5] = P::template cvt<1>(w.y);
+    v[6] = P::template cvt<2>(w.y); v[7] = P::template cvt<3>(w.y);
+}
+
 template <int CTRL, int RMASK>
 __device__ __forceinline__ float dpp_add(float v) {
     return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RMASK, 0xf, false));
@@ -46,12 +75,6 @@ __device__ __forceinline__ float wave_sum_f32(float v) {  // wave_sum_dpp's netw
     v = dpp_add<0x143, 0xc>(v);
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
-
-// ---- the routing workspace of the grouped expert GEMMs (mxm_route_kernel of mxfp4_moe.hip writes it; mxfp4_moe.hip and mxfp4_moe_a4.hip read it)
-// int32: head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P]
-constexpr int MXM_BM = 128;      // rows of a row tile
-constexpr int MXM_MAX_E = 1024;  // bins of the routing kernel's scan
-constexpr int MXM_HEAD = 4;      // int32 words before the tile table: [0] the tile count
 
 // ---- prefill forms: four code bytes -> one 8-k MFMA fragment at the block's rebiased scale ---------------------------------------------
 template <int DT> struct mx_frag;
@@ -73,5 +96,173 @@ template <> struct mx_frag<BIE_F16> {
     }
     static __device__ __forceinline__ float16_t mfma(const t& a, const t& b, const float16_t& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
+
+// ---- where the rows of a tile come from ------------------------------------------------------------------------------------------------
+// A tile GEMM body asks its row source, for tile row r: whether the row is live (a dead row loads as zero and is not stored), which
+// stored row of x (or of xq / xs / row_flag) it reads, and which row of y it writes.  src and dst are asked of live rows only.
+struct mx_rows_dense {  // rows m0 .. of an [M, K] x, written to the same rows of y
+    int m0, M;
+    __device__ __forceinline__ bool live(int r) const { return m0 + r < M; }
+    __device__ __forceinline__ long src(int r) const { return m0 + r; }
+    __device__ __forceinline__ long dst(int r) const { return m0 + r; }
+};
+struct mx_rows_listed {  // the pairs of a row tile of the grouped expert GEMMs: prow[] in LDS (-1 past the segment), pair p writes y[p]
+    const int* prow;
+    int S, x_per_pair;
+    __device__ __forceinline__ bool live(int r) const { return prow[r] >= 0; }
+    __device__ __forceinline__ long src(int r) const { return x_per_pair ? prow[r] : prow[r] / S; }
+    __device__ __forceinline__ long dst(int r) const { return prow[r]; }
+};
+
+// ---- the weight-only prefill tile ----------------------------------------------------------------------------------------------------------
+constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 64;
+constexpr int MX_APITCH = MX_BK * 2 + 16;  // bytes per x row in LDS (16-byte pad: the fragment reads of 32 rows spread over the banks)
+constexpr int MX_BPITCH = 36;              // bytes per weight row: 32 code bytes + 4 (9 dwords, the 32 rows of a read on distinct banks)
+constexpr int MX_STAGE = MX_BM * MX_APITCH + MX_BN * MX_BPITCH + MX_BN * 2 * 4;  // x, codes, the two fp32 rebiased scales per row
+
+// One 128 x 128 tile of y = x . W^T (+ bias) on v_mfma_f32_32x32x16_{bf16,f16}: tile rows from `rows`, columns n0 .. of the N weight
+// rows that start at row r0 of qw / sc / ecol / bias (0, or (long)e * N for expert e).  4 waves as 2 x 2, wave tile 64 x 64 (2 x 2 MFMA
+// tiles).  Per 64-k stage a thread loads 4 x 16 bytes of x, 16 code bytes and one scale byte into registers while the MFMAs run on the
+// other LDS buffer, then writes them (the scale already rebiased to fp32).  The weight tile is staged packed and converted to B
+// fragments after the LDS read: a lane's 8-k fragment is 4 code bytes = 4 converts.  Dead rows and whatever lies past N / K: x and
+// codes load as zero, scales as 1.0, so the padding adds exact zeros.  All 256 threads of the workgroup must call it together.
+template <int DT, class Rows>
+__device__ __forceinline__ void mx_gemm_tile(const Rows& rows, const uint16_t* __restrict__ x, const uint8_t* __restrict__ qw,
+                                             const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol, const void* __restrict__ bias,
+                                             void* __restrict__ y, long r0, int n0, int N, int K) {
+    typedef mx_frag<DT> F;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX_STAGE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int KT = (K + MX_BK - 1) / MX_BK, KB = K >> 5;
+
+    // this thread's load slots
+    const int bn = t >> 1, bh = t & 1;  // weight row bn of the tile, 16-byte half bh; scale block bh of the stage
+    const int nb = n0 + bn;
+    const bool nb_ok = nb < N;
+    const uint8_t* wsrc = qw + (r0 + min(nb, N - 1)) * (K >> 1) + bh * 16;
+    const uint8_t* ssrc = sc + (r0 + min(nb, N - 1)) * KB + bh;
+    const uint32_t e = nb_ok ? ecol[r0 + nb] : 0u;
+    const uint16_t* xrow[4];  // the x rows of this thread's four 16-byte pieces per stage: tile row (t + 256 i) / 8, piece t & 7
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = (t + 256 * i) >> 3;
+        xrow[i] = rows.live(row) ? x + rows.src(row) * K + (t & 7) * 8 : nullptr;
+    }
+    uint4_t ra[4], rb;
+    float rs;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            ra[i] = (xrow[i] && kt * MX_BK + (t & 7) * 8 < K) ? *reinterpret_cast<const uint4_t*>(xrow[i] + kt * MX_BK) : uint4_t{0u, 0u, 0u, 0u};
+        const bool kin = kt * MX_BK + bh * 32 < K;
+        rb = (nb_ok && kin) ? __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wsrc + kt * 32)) : uint4_t{0u, 0u, 0u, 0u};
+        rs = (nb_ok && kin) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), e) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MX_APITCH + c16 * 16) = ra[i];
+        }
+        uint32_t* wb = reinterpret_cast<uint32_t*>(st + MX_BM * MX_APITCH + bn * MX_BPITCH + bh * 16);
+        wb[0] = rb.x; wb[1] = rb.y; wb[2] = rb.z; wb[3] = rb.w;
+        reinterpret_cast<float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH)[bn * 2 + bh] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * MX_STAGE;
+        const float* ss = reinterpret_cast<const float*>(st + MX_BM * MX_APITCH + MX_BN * MX_BPITCH);
+#pragma unroll
+        for (int ks = 0; ks < MX_BK / 16; ks++) {
+            typename F::t a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX_APITCH + ks * 32 + hh * 16));
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int n = wx * 64 + j * 32 + rl;
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(st + MX_BM * MX_APITCH + n * MX_BPITCH + ks * 8 + hh * 4);
+                b[j] = F::cvt(w, ss[n * 2 + (ks >> 1)]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: column n = lane & 31, tile row (r & 3) + 8 (r >> 2) + 4 hh
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int n = n0 + wx * 64 + j * 32 + rl;
+        if (n >= N) continue;
+        const float cs = e8m0_f32(ecol[r0 + n]);
+        const float bv = bias ? dt_traits<DT>::load(bias, r0 + n) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (rows.live(row)) {
+                    float v = acc[i][j][r] * cs;
+                    if (bias) v += bv;
+                    dt_traits<DT>::store(y, rows.dst(row) * N + n, v);
+                }
+            }
+    }
+}
+
+// ---- the routing workspace of the grouped expert GEMMs (mxm_route_kernel of mxfp4_moe.hip writes it; mxfp4_moe.hip and mxfp4_moe_a4.hip read it)
+// int32: head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P]
+constexpr int MXM_BM = 128;      // rows of a row tile
+constexpr int MXM_MAX_E = 1024;  // bins of the routing kernel's scan
+constexpr int MXM_HEAD = 4;      // int32 words before the tile table: [0] the tile count
+
+// The start of a grouped GEMM workgroup: its (row tile, column tile of BN columns), the row tile's expert e and first column n0, and
+// the tile's pairs in prow[MXM_BM] (LDS; -1 past the segment), published by a barrier.  Workgroup -> tile: the workgroups of one XCD
+// (blockIdx.x & 7) walk the row tiles of one column tile after another, so the tiles of one expert, which follow each other in the
+// table, find the expert's BN columns of weights in that XCD's L2.  Returns false where the workgroup has no GEMM to run: a surplus
+// workgroup (beyond the tile count the routing kernel wrote), or a tile of the skipped bin, whose rows of y it has then zeroed.  Both
+// exits are workgroup-uniform and come before any address is formed from e.
+template <int DT, int BN>
+__device__ __forceinline__ bool mxm_tile_begin(const int32_t* __restrict__ ws, int max_tiles, int E, int N, void* __restrict__ y, int* prow, int& e, int& n0) {
+    const int t = threadIdx.x;
+    int bid = blockIdx.x;
+    {
+        const int nblk = gridDim.x, xcd = bid & 7, per = nblk >> 3, rem = nblk & 7;
+        bid = xcd * per + (xcd < rem ? xcd : rem) + (bid >> 3);
+    }
+    const int tile_m = bid % max_tiles, tile_n = bid / max_tiles;
+    if (tile_m >= ws[0]) return false;
+    e = ws[MXM_HEAD + tile_m];
+    const int first = ws[MXM_HEAD + max_tiles + tile_m], nrows = ws[MXM_HEAD + 2 * max_tiles + tile_m];
+    const int32_t* list = ws + MXM_HEAD + 3 * (long)max_tiles;
+    if (t < MXM_BM) prow[t] = t < nrows ? list[first + t] : -1;
+    __syncthreads();
+    n0 = tile_n * BN;
+    if (e < E) return true;
+    for (int i = t; i < MXM_BM * BN; i += 256) {
+        const int p = prow[i / BN], n = n0 + i % BN;
+        if (p >= 0 && n < N) dt_traits<DT>::store(y, (long)p * N + n, 0.0f);
+    }
+    return false;
+}
 
 }  // namespace bie

@@ -10,17 +10,17 @@
 // other pairs are and wherever routing places the row.  Every expert and row offset is 64-bit.  Nothing synchronises with the host: the
 // grids are sized from P and E, surplus workgroups leave after reading the tile count the routing kernel wrote.
 //
-// Routed decode form (mxm_decode_kernel, one launch): a workgroup per pair and C output columns, the arithmetic of mx_decode_kernel for
-// one row (v_cvt_scalef32_pk_*_fp4 at scale 1, v_dot2_f32_*, the block scale on the fp32 partial, DPP sums).  It reads idx[p] and
+// Routed decode form (mxm_decode_kernel, one launch): a workgroup per pair and C output columns, the arithmetic of mxfp4.hip's decode
+// form for one row (v_cvt_scalef32_pk_*_fp4 at scale 1, v_dot2_f32_*, the block scale on the fp32 partial, DPP sums).  It reads idx[p] and
 // offsets into that expert's rows.  Keeps the fp32 range of W, needs neither e_col nor a workspace.
 // Grouped prefill form (two launches):
 //   mxm_route_kernel, one workgroup: an LDS histogram of the pairs over the experts (the skipped pairs in a bin of their own), an
 //   exclusive scan, the tile table (expert, first entry, rows) with every expert's segment cut into row tiles of MXM_BM, and the pair
 //   list ordered by expert.  The order of the pairs inside a segment is that of the LDS atomics' arrival; no row of y depends on it.
-//   mxm_gemm_kernel: mx_gemm_kernel's 128 x 128 tile on v_mfma_f32_32x32x16_{f16,bf16} (packed codes staged in LDS, converted in
-//   registers, columns rebiased by e_col[e, n]).  A row tile belongs to one expert and gathers its x rows through the pair list, each
-//   row in whole 16-byte pieces; rows past the segment load as zero and are not stored; the epilogue scatters row r to y[pair r].  The
-//   tiles of the skipped bin run no K loop and store zeros.
+//   mxm_gemm_kernel: mxm_tile_begin and mx_gemm_tile of mxfp4_common.cuh, the 128 x 128 tile of the linear layer's prefill form (packed
+//   codes staged in LDS, converted in registers, columns rebiased by e_col[e, n]).  A row tile belongs to one expert and gathers its x
+//   rows through the pair list, each row in whole 16-byte pieces; rows past the segment load as zero and are not stored; the epilogue
+//   scatters row r to y[pair r].  The tiles of the skipped bin run no K loop and store zeros.
 #include "mxfp4_common.cuh"
 
 #pragma clang fp contract(off)
@@ -29,7 +29,7 @@ namespace bie {
 
 // ---- routed decode form -------------------------------------------------------------------------------------------------------------------
 // Workgroup: pair blockIdx.y, columns C * blockIdx.x .. + C - 1 of its expert (clamped reads past N, never stored).  Thread t takes the
-// 16-value units u = t, t + 256, ... of K, as in mx_decode_kernel.
+// 16-value units u = t, t + 256, ... of K: per column 8 code bytes and the scale byte of block u / 2.
 template <int DT, int C>
 __global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw,
                                                          const uint8_t* __restrict__ sc, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
@@ -71,10 +71,7 @@ __global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restr
 #pragma unroll
         for (int c = 0; c < C; c++) {
             typename P::t wv[8];
-            wv[0] = P::template cvt<0>(wb[c].x); wv[1] = P::template cvt<1>(wb[c].x);
-            wv[2] = P::template cvt<2>(wb[c].x); wv[3] = P::template cvt<3>(wb[c].x);
-            wv[4] = P::template cvt<0>(wb[c].y); wv[5] = P::template cvt<1>(wb[c].y);
-            wv[6] = P::template cvt<2>(wb[c].y); wv[7] = P::template cvt<3>(wb[c].y);
+            mx_unpack16<DT>(wb[c], wv);
             float s = 0.0f;
 #pragma unroll
             for (int j = 0; j < 8; j++) s = P::dot(wv[j], xv[j], s);
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restr
 }
 
 // ---- grouped prefill form: routing --------------------------------------------------------------------------------------------------------
-constexpr int MXM_BN = 128, MXM_BK = 64;  // MXM_BM, MXM_MAX_E and MXM_HEAD: mxfp4_common.cuh (the routing workspace's layout)
+static_assert(MXM_BM == MX_BM, "a row tile of the routing is a row tile of mx_gemm_tile");  // both: mxfp4_common.cuh
 
 // Workspace (int32): head [MXM_HEAD], tile_expert [max_tiles], tile_first [max_tiles], tile_rows [max_tiles], pair list [P].
 // max_tiles bounds sum_e ceil(count_e / BM) + ceil(skipped / BM): every tile holds a pair, and at most one tile per bin is not full.
@@ -180,135 +177,15 @@ __global__ __launch_bounds__(1024) void mxm_route_kernel(const int32_t* __restri
 }
 
 // ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
-constexpr int MXM_APITCH = MXM_BK * 2 + 16;  // as MX_APITCH / MX_BPITCH / MX_STAGE of mxfp4.hip
-constexpr int MXM_BPITCH = 36;
-constexpr int MXM_STAGE = MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH + MXM_BN * 2 * 4;
-
-// 4 waves as 2 x 2, wave tile 64 x 64, the stage pipeline of mx_gemm_kernel.  Workgroup -> (row tile, column tile): the workgroups of
-// one XCD (blockIdx.x & 7) walk the row tiles of one column tile after another, so the tiles of one expert, which follow each other in
-// the table, find the expert's 128 columns of weights in that XCD's L2.
+// A workgroup per (row tile of the table, column tile): mx_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
 template <int DT>
 __global__ __launch_bounds__(256) void mxm_gemm_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw,
                                                        const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol, const void* __restrict__ bias,
                                                        void* __restrict__ y, int S, int E, int N, int K, int x_per_pair, int max_tiles) {
-    typedef mx_frag<DT> F;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MXM_STAGE];
-    __shared__ int prow[MXM_BM];  // the tile's pairs, -1 past the segment
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = bid & 7, per = nblk >> 3, rem = nblk & 7;
-        bid = xcd * per + (xcd < rem ? xcd : rem) + (bid >> 3);
-    }
-    const int tile_m = bid % max_tiles, tile_n = bid / max_tiles;
-    if (tile_m >= ws[0]) return;  // a surplus workgroup (uniform)
-    const int e = ws[MXM_HEAD + tile_m], first = ws[MXM_HEAD + max_tiles + tile_m], rows = ws[MXM_HEAD + 2 * max_tiles + tile_m];
-    const int32_t* list = ws + MXM_HEAD + 3 * (long)max_tiles;
-    if (t < MXM_BM) prow[t] = t < rows ? list[first + t] : -1;
-    __syncthreads();
-    const int n0 = tile_n * MXM_BN;
-    if (e >= E) {  // the skipped bin: zero rows
-        for (int i = t; i < MXM_BM * MXM_BN; i += 256) {
-            const int p = prow[i / MXM_BN], n = n0 + i % MXM_BN;
-            if (p >= 0 && n < N) dt_traits<DT>::store(y, (long)p * N + n, 0.0f);
-        }
-        return;
-    }
-    const int KT = (K + MXM_BK - 1) / MXM_BK, KB = K >> 5;
-    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
-
-    // this thread's load slots
-    const int bn = t >> 1, bh = t & 1;  // weight row bn of the tile, 16-byte half bh; scale block bh of the stage
-    const int nb = n0 + bn;
-    const bool nb_ok = nb < N;
-    const uint8_t* wsrc = qw + (r0 + min(nb, N - 1)) * (K >> 1) + bh * 16;
-    const uint8_t* ssrc = sc + (r0 + min(nb, N - 1)) * KB + bh;
-    const uint32_t ec = nb_ok ? ecol[r0 + nb] : 0u;
-    const uint16_t* xrow[4];  // the gathered x rows of this thread's four 16-byte pieces per stage
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int p = prow[(t + 256 * i) >> 3];
-        xrow[i] = p >= 0 ? x + (long)(x_per_pair ? p : p / S) * K + (t & 7) * 8 : nullptr;
-    }
-    uint4_t ra[4], rb;
-    float rs;
-    auto load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            ra[i] = (xrow[i] && kt * MXM_BK + (t & 7) * 8 < K) ? *reinterpret_cast<const uint4_t*>(xrow[i] + kt * MXM_BK) : uint4_t{0u, 0u, 0u, 0u};
-        const bool kin = kt * MXM_BK + bh * 32 < K;
-        rb = (nb_ok && kin) ? __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wsrc + kt * 32)) : uint4_t{0u, 0u, 0u, 0u};
-        rs = (nb_ok && kin) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), ec) : 1.0f;
-    };
-    auto store = [&](int buf) {
-        unsigned char* st = lds + buf * MXM_STAGE;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
-            *reinterpret_cast<uint4_t*>(st + row * MXM_APITCH + c16 * 16) = ra[i];
-        }
-        uint32_t* wb = reinterpret_cast<uint32_t*>(st + MXM_BM * MXM_APITCH + bn * MXM_BPITCH + bh * 16);
-        wb[0] = rb.x; wb[1] = rb.y; wb[2] = rb.z; wb[3] = rb.w;
-        reinterpret_cast<float*>(st + MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH)[bn * 2 + bh] = rs;
-    };
-
-    float16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
-
-    const int rl = lane & 31, hh = lane >> 5;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < KT; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < KT) load(kt + 1);
-        const unsigned char* st = lds + buf * MXM_STAGE;
-        const float* ss = reinterpret_cast<const float*>(st + MXM_BM * MXM_APITCH + MXM_BN * MXM_BPITCH);
-#pragma unroll
-        for (int ks = 0; ks < MXM_BK / 16; ks++) {
-            typename F::t a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MXM_APITCH + ks * 32 + hh * 16));
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int n = wx * 64 + j * 32 + rl;
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(st + MXM_BM * MXM_APITCH + n * MXM_BPITCH + ks * 8 + hh * 4);
-                b[j] = F::cvt(w, ss[n * 2 + (ks >> 1)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
-        }
-        if (kt + 1 < KT) store(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D: column n = lane & 31, tile row (r & 3) + 8 (r >> 2) + 4 hh, scattered to y[pair of the row]
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int n = n0 + wx * 64 + j * 32 + rl;
-        if (n >= N) continue;
-        const float cs = e8m0_f32(ecol[r0 + n]);
-        const float bv = bias ? dt_traits<DT>::load(bias, r0 + n) : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int p = prow[wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh];
-                if (p >= 0) {
-                    float v = acc[i][j][r] * cs;
-                    if (bias) v += bv;
-                    dt_traits<DT>::store(y, (long)p * N + n, v);
-                }
-            }
-    }
+    __shared__ int prow[MXM_BM];
+    int e, n0;
+    if (!mxm_tile_begin<DT, MX_BN>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
+    mx_gemm_tile<DT>(mx_rows_listed{prow, S, x_per_pair}, x, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
 }
 
 // ---- plan and launcher --------------------------------------------------------------------------------------------------------------------
@@ -364,7 +241,7 @@ int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* q
     const int max_tiles = (int)mxm_max_tiles(P, E);
     int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
     if (rc) return rc;
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, MXM_BN)));
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, MX_BN)));
     if (dtype == BIE_F16)
         hipLaunchKernelGGL(mxm_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
     else

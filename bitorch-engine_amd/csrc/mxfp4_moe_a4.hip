@@ -12,17 +12,15 @@
 // row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
 //
 // Routed decode form (mxma4_decode_kernel, P <= 1024): a workgroup per pair and strip of 16 C16 columns of its expert, K split over the
-// 4 waves in 128-k steps as in mxa4_decode_kernel, on v_mfma_scale_f32_16x16x128_f8f6f4.  The pair's row is row 0 of the x operand,
+// 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4.  The pair's row is row 0 of the x operand,
 // rows 1 .. 15 are zero codes under scale code 127; the four partial sums meet in LDS.  FUSED (one launch, K <= MXMA4_ONE_K): the
 // workgroup quantises x_row(p) into LDS itself (a4_quantize_unit, the bits of mxa4_quantize_kernel; codes, scale bytes, and the
 // non-finite flag through the barrier) and reads neither xq nor a workspace.  Not FUSED: it reads xq / xs / row_flag from memory.
 // Grouped prefill form: mxa4_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
-// mxma4_gemm_kernel: mxa4_gemm_kernel's 128 x 128 tile, stage layout and operand placement on v_mfma_scale_f32_32x32x64_f8f6f4 (the
-// weight fragment is the A operand, the lane's scale in byte 0).  A row tile belongs to one expert, gathers the xq / xs rows of its
-// pairs through the pair list (whole 16-byte pieces of codes, whole scale bytes) and reads weights from (long)e * N; rows past the
-// segment enter as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the
-// skipped bin run no K loop and store zeros.  Workgroup -> tile walk per XCD as in mxm_gemm_kernel.
-#include "mxfp4_common.cuh"
+// mxma4_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mxa4_gemm_tile (mxfp4_a4_common.cuh) at 128 x 128, the tile of the W4A4 linear
+// layer's prefill form.  A row tile belongs to one expert, gathers the xq / xs rows of its pairs through the pair list (whole 16-byte
+// pieces of codes, whole scale bytes) and reads weights from (long)e * N; rows past the segment enter as zero codes under scale code
+// 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no K loop and store zeros.
 #include "mxfp4_a4_common.cuh"
 
 #pragma clang fp contract(off)
@@ -140,178 +138,19 @@ __global__ __launch_bounds__(256) void mxma4_decode_kernel(const void* __restric
 }
 
 // ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
-constexpr int MXMA4_BN = 128, MXMA4_BK = 128;          // k per stage: 64 code bytes and 4 scale bytes per row
-constexpr int MXMA4_PITCH = MXMA4_BK / 2 + 16;         // as A4_PITCH of mxfp4_a4.hip
-constexpr int MXMA4_ROWS = MXM_BM + MXMA4_BN;          // rows of the stage image: 0 .. MXM_BM - 1 = x, the rest = weights
-constexpr int MXMA4_NLD = MXMA4_ROWS * 4 / 256;        // 16-byte pieces per thread and stage: row = piece / 4, quarter = piece % 4
-constexpr int MXMA4_STAGE = MXMA4_ROWS * MXMA4_PITCH + MXMA4_ROWS * 4;
-static_assert(MXMA4_ROWS == 256, "one scale dword per thread and stage");
+constexpr int MXMA4_W = 2;  // WM = WN of the tile: 128 x 128
+static_assert(64 * MXMA4_W == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
 
-// 4 waves as 2 x 2, wave tile 64 x 64 (mxa4_gemm_kernel with WM = WN = 2).  Workgroup -> (row tile, column tile): the workgroups of one
-// XCD (blockIdx.x & 7) walk the row tiles of one column tile after another, so the tiles of one expert, which follow each other in the
-// table, find the expert's 128 columns of weights in that XCD's L2.
+// A workgroup per (row tile of the table, column tile): mxa4_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
 template <int DT>
 __global__ __launch_bounds__(256) void mxma4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                          const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
                                                          const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
                                                          int N, int K, int x_per_pair, int max_tiles) {
-    constexpr int BM = MXM_BM, WM = 2, WN = 2;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MXMA4_STAGE];
-    __shared__ int prow[BM];  // the tile's pairs, -1 past the segment
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
-    int bid = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = bid & 7, per = nblk >> 3, rem = nblk & 7;
-        bid = xcd * per + (xcd < rem ? xcd : rem) + (bid >> 3);
-    }
-    const int tile_m = bid % max_tiles, tile_n = bid / max_tiles;
-    if (tile_m >= ws[0]) return;  // a surplus workgroup (uniform)
-    const int e = ws[MXM_HEAD + tile_m], first = ws[MXM_HEAD + max_tiles + tile_m], rows = ws[MXM_HEAD + 2 * max_tiles + tile_m];
-    const int32_t* list = ws + MXM_HEAD + 3 * (long)max_tiles;
-    if (t < BM) prow[t] = t < rows ? list[first + t] : -1;
-    __syncthreads();
-    const int n0 = tile_n * MXMA4_BN;
-    if (e >= E) {  // the skipped bin: zero rows
-        for (int i = t; i < BM * MXMA4_BN; i += 256) {
-            const int p = prow[i / MXMA4_BN], n = n0 + i % MXMA4_BN;
-            if (p >= 0 && n < N) dt_traits<DT>::store(y, (long)p * N + n, 0.0f);
-        }
-        return;
-    }
-    const int KB = K >> 5, KT = (K + MXMA4_BK - 1) / MXMA4_BK;
-    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
-
-    // load slots: pieces t, t + 256, ... of the stage image; thread t also loads row t's four scale bytes
-    const uint8_t* csrc[MXMA4_NLD];
-    bool cok[MXMA4_NLD];
-#pragma unroll
-    for (int i = 0; i < MXMA4_NLD; i++) {
-        const int row = (t + 256 * i) >> 2;
-        if (row < BM) {
-            const int p = prow[row];
-            cok[i] = p >= 0;
-            csrc[i] = xq + (long)(p < 0 ? 0 : x_per_pair ? p : p / S) * (K >> 1);
-        } else {
-            cok[i] = n0 + row - BM < N;
-            csrc[i] = qw + (r0 + min(n0 + row - BM, N - 1)) * (K >> 1);
-        }
-    }
-    bool sok;
-    const uint8_t* ssrc;
-    if (t < BM) {
-        const int p = prow[t];
-        sok = p >= 0;
-        ssrc = xs + (long)(p < 0 ? 0 : x_per_pair ? p : p / S) * KB;
-    } else {
-        sok = n0 + t - BM < N;
-        ssrc = sc + (r0 + min(n0 + t - BM, N - 1)) * KB;
-    }
-    uint4_t rc[MXMA4_NLD];
-    uint32_t rs = 0x7f7f7f7fu;
-    auto load = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < MXMA4_NLD; i++) {
-            const int kb = kt * 4 + ((t + 256 * i) & 3);
-            rc[i] = (cok[i] && kb < KB) ? *reinterpret_cast<const uint4_t*>(csrc[i] + (long)kb * 16) : uint4_t{0u, 0u, 0u, 0u};
-        }
-        rs = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int kb = kt * 4 + j;
-            const uint32_t s = (sok && kb < KB) ? (uint32_t)ssrc[kb] : 127u;
-            rs |= s << (8 * j);
-        }
-    };
-    auto store = [&](int buf) {
-        unsigned char* st = lds + buf * MXMA4_STAGE;
-#pragma unroll
-        for (int i = 0; i < MXMA4_NLD; i++) {
-            const int q = t + 256 * i;
-            *reinterpret_cast<uint4_t*>(st + (q >> 2) * MXMA4_PITCH + (q & 3) * 16) = rc[i];
-        }
-        reinterpret_cast<uint32_t*>(st + MXMA4_ROWS * MXMA4_PITCH)[t] = rs;
-    };
-
-    float16_t acc[WN][WM];  // [weight row block j][x row block i]: D rows = columns n of y, D columns = rows of the tile
-#pragma unroll
-    for (int j = 0; j < WN; j++)
-#pragma unroll
-        for (int i = 0; i < WM; i++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[j][i][r] = 0.0f;
-
-    const int rl = lane & 31, hh = lane >> 5;
-    load(0);
-    store(0);
-    __syncthreads();
-    for (int kt = 0; kt < KT; kt++) {
-        const int buf = kt & 1;
-        if (kt + 1 < KT) load(kt + 1);
-        const unsigned char* st = lds + buf * MXMA4_STAGE;
-        const uint32_t* ss = reinterpret_cast<const uint32_t*>(st + MXMA4_ROWS * MXMA4_PITCH);
-        uint32_t sxa[WM], swa[WN];  // the row's four scale bytes, shifted so that this lane's block of k-step ks sits in byte 2 ks
-#pragma unroll
-        for (int i = 0; i < WM; i++) sxa[i] = ss[wy * 32 * WM + i * 32 + rl] >> (8 * hh);
-#pragma unroll
-        for (int j = 0; j < WN; j++) swa[j] = ss[BM + wx * 32 * WN + j * 32 + rl] >> (8 * hh);
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            mxa4_v8i fx[WM], fw[WN];
-#pragma unroll
-            for (int i = 0; i < WM; i++)
-                fx[i] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (wy * 32 * WM + i * 32 + rl) * MXMA4_PITCH + (ks * 2 + hh) * 16));
-#pragma unroll
-            for (int j = 0; j < WN; j++)
-                fw[j] = a4_frag(*reinterpret_cast<const uint4_t*>(st + (BM + wx * 32 * WN + j * 32 + rl) * MXMA4_PITCH + (ks * 2 + hh) * 16));
-#pragma unroll
-            for (int j = 0; j < WN; j++)
-#pragma unroll
-                for (int i = 0; i < WM; i++)
-                    acc[j][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[j], fx[i], acc[j][i], 4, 4, 0, (int)((swa[j] >> (16 * ks)) & 0xffu), 0,
-                                                                                (int)((sxa[i] >> (16 * ks)) & 0xffu));
-        }
-        if (kt + 1 < KT) store(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D: D column (= tile row) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh: registers 4q .. 4q + 3 are four
-    // consecutive n of one pair -> one 8-byte store where N allows it; row r of the tile goes to y[pair r]
-    const bool vec = (N & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < WM; i++) {
-        const int p = prow[wy * 32 * WM + i * 32 + rl];
-        if (p < 0) continue;
-        const bool rbad = row_flag[x_per_pair ? p : p / S] != 0;
-#pragma unroll
-        for (int j = 0; j < WN; j++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int n = n0 + wx * 32 * WN + j * 32 + 8 * q + 4 * hh;
-                if (n >= N) continue;
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    v[r] = acc[j][i][4 * q + r];
-                    if (n + r < N) {
-                        if (rbad || ecol[r0 + n + r] == 255u) v[r] = a4_nan();
-                        if (bias) v[r] += dt_traits<DT>::load(bias, r0 + n + r);
-                    }
-                }
-                if (vec) {
-                    uint16_t h[4];
-                    dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
-                    dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
-                    uint2_t o;
-                    o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-                    o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-                    *reinterpret_cast<uint2_t*>(reinterpret_cast<uint16_t*>(y) + (long)p * N + n) = o;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        if (n + r < N) dt_traits<DT>::store(y, (long)p * N + n + r, v[r]);
-                }
-            }
-    }
+    __shared__ int prow[MXM_BM];
+    int e, n0;
+    if (!mxm_tile_begin<DT, 64 * MXMA4_W>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
+    mxa4_gemm_tile<DT, MXMA4_W, MXMA4_W>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
@@ -387,7 +226,7 @@ int mxfp4_moe_a4_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t
     if (rc) return rc;
     const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
     const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, MXMA4_BN)));
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * MXMA4_W)));
     if (dtype == BIE_F16)
         hipLaunchKernelGGL(mxma4_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
                            x_per_pair, max_tiles);

@@ -242,6 +242,33 @@ def test_exact_data_is_bit_identical_across_forms_and_to_the_sibling_layers(T, x
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("xpp", [0, 1])
+def test_grouped_prefill_form_equals_the_dense_prefill_form_bit_for_bit_on_inexact_data(xpp, dt):
+    """Random normal x (quantised once, by quantize_act), random weights and a bias: the sums round, and the grouped prefill form still
+    gives the bits of the W4A4 linear layer's prefill form called once per expert on that expert's rows, because both run the one tile
+    body (mxa4_gemm_tile) and a row's sum order is fixed by K alone; the linear layer takes 64 x 64 tiles at this size, which moves an
+    element to another lane, not its sum to another order.  K = 160 is not a whole 128-k stage, N = 130 gives two column tiles with the
+    second partial, and the routing holds an expert with more than one row tile and a partial one beside an expert without pairs."""
+    from bitorch_engine.extensions import mxfp4_a4_linear_cuda
+    E, S, K, N, T = 3, 2, 160, 130, 70
+    q, s, _ = rand_mx(E, N, K, 91)
+    g = torch.Generator().manual_seed(92 + xpp)
+    x = torch.randn((T, S, K) if xpp else (T, K), generator=g).to(dt).to(DEV)
+    bias = torch.randn((E, N), generator=g).to(dt).to(DEV)
+    idx = make_idx(T, S, E, 93)
+    assert_coverage(idx, E)
+    cq, cs, cf = ext().quantize_act(x.reshape(-1, K))
+    y = ext().gemm(cq, cs, cf, idx.to(DEV), q, s, bias, dtype=dt, form=1)
+    rows = torch.zeros((T * S, N), dtype=dt, device=DEV)  # a skipped slot is +0
+    for e in range(E):
+        sel = (idx.reshape(-1) == e).nonzero().reshape(-1).to(DEV)
+        if sel.numel():
+            r = sel if xpp else sel // S  # the stored row of every pair
+            rows[sel] = mxfp4_a4_linear_cuda.gemm(cq[r], cs[r], cf[r], q[e], s[e], bias[e], dtype=dt, form=1)
+    assert torch.equal(y.view(torch.int16), rows.reshape(T, S, N).view(torch.int16))
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("xpp", [0, 1])
 @pytest.mark.parametrize("form", [0, 1])
 def test_a_row_depends_on_its_own_pair_only(form, xpp, dt):
     E, S, K, N, T = 8, 4, 288, 130, 60
