@@ -1,0 +1,242 @@
+// MXFP4 W4A8 linear layer for gfx950: the MXFP4 weights of mxfp4.hip against activations quantised to MXFP8 (E4M3 elements, E8M0 block
+// scales) on the fly, contracted on the block-scaled matrix instructions with an FP4 A operand and an E4M3 B operand
+// (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A8 linear layer").
+//
+//   xq uint8 [M, K], xs uint8 [M, K/32]: x quantised per row and block of 32 by the OCP MX v1.0 rule with E4M3 elements (emax = 8):
+//       e = clamp(floor(log2 amax) - 8, -127, 127), code = e4m3fn(clamp(v * 2^-e, +-448)) round to nearest even, never a NaN code
+//   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (its codes are unspecified), else 0
+//   y[m, n] = dt( sum_b 2^(xs[m, b] + scales[n, b] - 254) * (sum_{k in b} e4m3(xq) * e2m1(qweight)) + bias[n] )
+//   y[m, :] = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255 (a weight block with scale code 255)
+//
+// How the instructions read a mixed pair of operands was pinned on the card by tools/probe/probe_mx_a8.hip
+// (profiles/mxfp4_a8_probe.txt), A = FP4 (cbsz 4, four VGPRs), B = E4M3 (blgp 0, eight VGPRs).  The FP4 operand is read as in the
+// W4A4 kernels: lane group g (l >> 5 in v_mfma_scale_f32_32x32x64_f8f6f4, l >> 4 in v_mfma_scale_f32_16x16x128_f8f6f4) holds the
+// elements k = 32 g .. 32 g + 31 of the instruction's K.  The E4M3 operand is NOT one block per lane: with G = 2 / 4 lane groups,
+// group g holds k = 16 g .. + 15 in bytes 0 .. 15 and k = 16 G + 16 g .. + 15 in bytes 16 .. 31.  xq stays row-major E4M3 in memory
+// and nothing is permuted in registers: a lane loads its two 16-byte halves from two places of the row (a8_frag of
+// mxfp4_a8_common.cuh).  The scale byte of lane group g applies to block g of the instruction's K on either operand; the kernels keep
+// it in byte 0 of the scale register (byte select 0).  The one-hot selector test of tests/test_mxfp4_a8_gpu.py holds the element map
+// in the suite.
+//
+// Quantise kernel (mxa8_quantize_kernel): a workgroup per row of x, a block of 32 per 4 lanes (16-byte loads, 8 bytes of codes per
+// lane), the block maximum over the 4 lanes on the DPP network, the row's non-finite flag through the workgroup's barrier.
+// Decode form (mxa8_decode_kernel, M <= 64): a workgroup per 16 output columns, K split over its 4 waves; every wave loads its weight
+// fragments straight from qweight (non-temporal, 16 bytes per lane) and the x fragments from xq (two 16-byte loads 64 bytes apart),
+// one 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS in a fixed order.
+// Prefill form (mxa8_gemm_kernel): mxa8_gemm_tile of mxfp4_a8_common.cuh, a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2,
+// codes and scale bytes staged through registers into double-buffered LDS (128 k per stage), on the rows m0 .. of xq / xs.
+#include "mxfp4_a8_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// ---- activation quantiser -------------------------------------------------------------------------------------------------------------
+// Workgroup = one row.  Thread t takes the 8-value units t, t + 256, ... of the row; the 4 lanes of a quad hold one block of 32.
+template <int DT>
+__global__ __launch_bounds__(256) void mxa8_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ xq, uint8_t* __restrict__ xs,
+                                                            uint8_t* __restrict__ row_flag, int K) {
+    const long m = blockIdx.x;
+    const uint16_t* xr = x + m * K;
+    uint2_t* qr = reinterpret_cast<uint2_t*>(xq + m * K);
+    uint8_t* sr = xs + m * (K >> 5);
+    const int U = K >> 3;  // a multiple of 4: whole quads are in or out
+    int bad = 0;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint2_t codes;
+        uint32_t scode;
+        a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
+        qr[u] = codes;
+        if ((u & 3) == 0) sr[u >> 2] = (uint8_t)scode;
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) row_flag[m] = (uint8_t)(bad ? 1 : 0);
+}
+
+// ---- decode form ------------------------------------------------------------------------------------------------------------------------
+// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
+// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15, block l >> 4 of the step's weights and x scales, and the x bytes
+// 16 (l >> 4) .. + 15 and 64 + 16 (l >> 4) .. + 15 of the step (a8_frag).  Blocks past K and rows past M enter as zero codes under
+// scale 2^0 (code 127).  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one
+// row of y.
+template <int DT, int G>
+__global__ __launch_bounds__(256) void mxa8_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                          const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                          const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
+    __shared__ mxa4_v4f red[3][G][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const int n0 = blockIdx.x * 16;
+    const long nl = min(n0 + r16, N - 1);
+    const uint8_t* wrow = qw + nl * (K >> 1);
+    const uint8_t* srow = sc + nl * KB;
+    mxa4_v4f acc[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t w = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow) + kc);
+        int sw = __builtin_nontemporal_load(srow + kc);
+        // this lane's x halves: 16 bytes of block b0 = kq >> 1 of the step and 16 bytes of block b0 + 2, at offset 16 (kq & 1) in each
+        const int kb0 = s * 4 + (kq >> 1), kb1 = kb0 + 2;
+        const bool in0 = kb0 < KB, in1 = kb1 < KB;
+        const int o0 = min(kb0, KB - 1) * 32 + (kq & 1) * 16, o1 = min(kb1, KB - 1) * 32 + (kq & 1) * 16;
+        uint4_t a0[G], a1[G];
+        int sa[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const long m = min(g * 16 + r16, M - 1);
+            a0[g] = *reinterpret_cast<const uint4_t*>(xq + m * K + o0);
+            a1[g] = *reinterpret_cast<const uint4_t*>(xq + m * K + o1);
+            sa[g] = xs[m * KB + kc];
+        }
+        if (!kin) {
+            w = uint4_t{0u, 0u, 0u, 0u};
+            sw = 127;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const bool dead = g * 16 + r16 >= M;
+            if (!in0 || dead) a0[g] = uint4_t{0u, 0u, 0u, 0u};
+            if (!in1 || dead) a1[g] = uint4_t{0u, 0u, 0u, 0u};
+            if (!kin || dead) sa[g] = 127;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(w), a8_frag(a0[g], a1[g]), acc[g], 4, 0, 0, sw, 0, sa[g]);
+    }
+    if (wave) {
+#pragma unroll
+        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
+    }
+    __syncthreads();
+    if (wave) return;
+    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y
+    const int n = n0 + 4 * kq;
+    if (n >= N) return;
+    const bool vec = (N & 3) == 0;
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const int m = g * 16 + r16;
+        if (m >= M) continue;
+        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
+        const bool rbad = row_flag[m] != 0;
+        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
+            if (n + r < N) {
+                if (rbad || ecol[n + r] == 255u) v[r] = a4_nan();
+                if (bias) v[r] += dt_traits<DT>::load(bias, n + r);
+            }
+        }
+        if (vec) {
+            uint16_t h[4];
+            dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
+            dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
+            uint2_t o;
+            o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+            o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+            *reinterpret_cast<uint2_t*>(yr + n) = o;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (n + r < N) dt_traits<DT>::store(yr, n + r, v[r]);
+        }
+    }
+}
+
+// ---- prefill form -----------------------------------------------------------------------------------------------------------------------
+// A workgroup per (64 WM) x (64 WN) tile (mxa8_gemm_tile), the tiles walked in pipe_tile's order.
+template <int DT, int WM, int WN>
+__global__ __launch_bounds__(256) void mxa8_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                        const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                        const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
+    int tile_m, tile_n;
+    pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
+    mxa8_gemm_tile<DT, WM, WN>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The decode form serves M <= A8_DECODE_ROWS (instances of 16, 32 and 64 rows); larger M takes the prefill form.  The plan's bound was
+// measured (tools/mxfp4_a8_bench.py, profiles/mxfp4_a8_bench.jsonl, the "sweep" rows, both forms forced at M = 8 .. 64, the quantise
+// launch included, fp16 and bf16 alike): the decode form was ahead at every M <= 32 on 4096 x 4096, 4096 -> 11008 and 11008 -> 4096
+// (0.26 - 0.76 x the prefill form's time), and at M = 48 and 64 on two of the three shapes (M = 64: 22.8 / 42.8 us against 40.0 / 85.8);
+// on 4096 -> 11008 it was 3 % behind at M = 48 (40.5 against 39.4 us) and 17 % behind at M = 64 (47.2 against 40.4).  The bound stays
+// at 64: what the prefill form would lose there on the other two shapes (75 % and 100 %) outweighs that.
+constexpr int A8_DECODE_ROWS = 64;
+constexpr int A8_PLAN_ROWS = 64;
+
+bool mxfp4_a8_decode_ok(long M) { return M >= 1 && M <= A8_DECODE_ROWS; }
+
+int mxfp4_a8_form(long M, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_A8_FORM", -1);
+    if (f == 0 && M <= A8_DECODE_ROWS) return 0;
+    if (f == 1) return 1;
+    return M <= A8_PLAN_ROWS ? 0 : 1;
+}
+
+// Workspace of bie_mxfp4_a8_linear_forward: xq [M, K] (16-byte aligned; M * K is a multiple of 32), xs [M, K/32], row_flag [M]
+static size_t a8_xs_offset(long M, long K) { return (size_t)(M * K); }
+static size_t a8_flag_offset(long M, long K) { return a8_xs_offset(M, K) + (size_t)(M * (K / 32)); }
+size_t mxfp4_a8_workspace_bytes(long M, long K) { return (a8_flag_offset(M, K) + (size_t)M + 15) / 16 * 16; }
+
+int mxfp4_a8_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st) {
+    const uint16_t* xp = reinterpret_cast<const uint16_t*>(x);
+    if (dtype == BIE_F16) hipLaunchKernelGGL(mxa8_quantize_kernel<BIE_F16>, dim3((unsigned)M), dim3(256), 0, st, xp, xq, xs, row_flag, (int)K);
+    else hipLaunchKernelGGL(mxa8_quantize_kernel<BIE_BF16>, dim3((unsigned)M), dim3(256), 0, st, xp, xq, xs, row_flag, (int)K);
+    return check_launch("mxa8_quantize_kernel");
+}
+
+template <int DT, int WM, int WN>
+static void a8_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                             const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const int tn = cdiv(N, 64 * WN);
+    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
+    hipLaunchKernelGGL((mxa8_gemm_kernel<DT, WM, WN>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
+}
+
+template <int DT>
+static void a8_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    // 128 x 128 tiles where they give every CU of the card (256) at least two workgroups, else 64 x 64 tiles, as in the W4A4 launcher
+    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) a8_gemm_launch_t<DT, 2, 2>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+    else a8_gemm_launch_t<DT, 1, 1>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+}
+
+template <int DT>
+static void a8_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                                const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv(N, 16));
+    if (M <= 16) hipLaunchKernelGGL((mxa8_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else if (M <= 32) hipLaunchKernelGGL((mxa8_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else hipLaunchKernelGGL((mxa8_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+}
+
+int mxfp4_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                         const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
+    if (form == 0) {
+        if (dtype == BIE_F16) a8_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        else a8_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        return check_launch("mxa8_decode_kernel");
+    }
+    if (dtype == BIE_F16) a8_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    else a8_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    return check_launch("mxa8_gemm_kernel");
+}
+
+int mxfp4_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
+                            long N, long K, int dtype, int form, hipStream_t st) {
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a8_xs_offset(M, K);
+    uint8_t* rf = xq + a8_flag_offset(M, K);
+    const int rc = mxfp4_a8_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_a8_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+}
+
+}  // namespace bie

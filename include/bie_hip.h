@@ -606,6 +606,34 @@ int bie_mxfp4_a4_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp4_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 w4a8
+ * MXFP4 weights x activations quantised to MXFP8 (E4M3 elements, E8M0 block scales) on the fly, contracted on the block-scaled matrix
+ * instructions with an FP4 and an E4M3 operand (MXFP4A8LinearCuda; INTEGRATION.md, "MXFP4 W4A8 linear layer").  qweight / scales / e_col
+ * are those of the mxfp4 section above, unchanged.
+ *   xq       uint8 [M, K]: row-major OCP E4M3 (e4m3fn) bytes; xs uint8 [M, K/32]: E8M0 codes.  Per row and block of 32, in fp32:
+ *            e = clamp(floor(log2 amax) - 8, -127, 127), xs = e + 127, xq = e4m3(clamp(x * 2^-e, -448, 448)) rounded to nearest even
+ *            with the sign kept (-0.0 -> 0x80); an all-zero block has scale code 0 and zero bytes; a NaN code (0x7F / 0xFF) is never
+ *            produced (bit-exact for finite x against tests/mxfp4_a8_ref.py)
+ *   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (the row's codes are then unspecified), else 0
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e4m3(xq[m,k]) * e2m1(qweight[n,k])) + bias[n] ): sums in fp32 in
+ *              any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ * bie_mxfp8_quantize_act: x [M, K] (dtype 0/1, 16-byte aligned) -> xq (16-byte aligned), xs, row_flag.
+ * bie_mxfp4_a8_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP4_A8_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mxfp4_a8_workspace_bytes: the bytes bie_mxfp4_a8_linear_forward needs: xq [M, K] (16-byte aligned), then xs, then row_flag, the
+ *   whole rounded up to 16 (any form); 0 for a shape the layer refuses.  Host only.  bie_mxfp4_a8_gemm needs no workspace (NULL is accepted).
+ * bie_mxfp4_a8_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction.  form -1 =
+ *   bie_mxfp4_a8_form.  e_col (bie_mxfp4_col_exp) is required by both forms.
+ * bie_mxfp4_a8_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call; nothing synchronises with the host. */
+int bie_mxfp8_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream);
+int bie_mxfp4_a8_form(long M, long N, long K, int dtype);
+size_t bie_mxfp4_a8_workspace_bytes(long M, long N, long K, int form);
+int bie_mxfp4_a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                                void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mxfp4_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                      const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp4 mixture of experts
  * The expert GEMM of a mixture-of-experts MLP on stacked MXFP4 weights (MXFP4ExpertsLinearCuda, MXFP4MoECuda; INTEGRATION.md, "MXFP4
  * mixture-of-experts layer").  T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p].
