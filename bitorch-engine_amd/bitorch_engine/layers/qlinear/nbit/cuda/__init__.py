@@ -7,4 +7,5 @@ from .mxfp4_a4_layer import MXFP4A4LinearCuda, MXFP4A4LinearForward
 from .mxfp4_a8_layer import MXFP4A8LinearCuda, MXFP4A8LinearForward
 from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda, MXFP4ExpertsLinearForward
 from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda, MXFP4A4ExpertsLinearForward
+from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda, MXFP4A8ExpertsLinearForward
 from .mxfp4_moe_layer import MXFP4MoECuda

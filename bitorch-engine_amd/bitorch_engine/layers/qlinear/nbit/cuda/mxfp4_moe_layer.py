@@ -13,12 +13,16 @@ a graph.  The activation and the combine are torch ops (fusing them into the ker
 
 activations="mxfp4" ("MXFP4 W4A4 mixture-of-experts layer"): gate_up and down are MXFP4A4ExpertsLinearCuda, which
 quantise x and a to MXFP4 per row and block of 32 and contract on the block-scaled matrix instructions (csrc/mxfp4_moe_a4.hip); the
-router, the top-k softmax, the SwiGLU and the combine are the same ops.  The default "dtype" is the block above, untouched."""
+router, the top-k softmax, the SwiGLU and the combine are the same ops.
+activations="mxfp8" ("MXFP4 W4A8 mixture-of-experts layer"): gate_up and down are MXFP4A8ExpertsLinearCuda, which
+quantise x and a to MXFP8 (E4M3 elements, E8M0 block scales) per row and block of 32 and contract on the same instructions with an FP4
+and an E4M3 operand (csrc/mxfp4_moe_a8.hip); everything else is the same ops.  The default "dtype" is the block above, untouched."""
 import torch
 from torch import nn
 
 from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda
 from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda
+from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda
 
 
 def swiglu(h: torch.Tensor, limit: float, alpha: float) -> torch.Tensor:
@@ -34,6 +38,9 @@ def combine(w: torch.Tensor, o: torch.Tensor) -> torch.Tensor:
     return (w.float()[..., None] * o.float()).sum(dim=1).to(o.dtype)
 
 
+_EXPERTS = {"dtype": MXFP4ExpertsLinearCuda, "mxfp4": MXFP4A4ExpertsLinearCuda, "mxfp8": MXFP4A8ExpertsLinearCuda}
+
+
 class MXFP4MoECuda(nn.Module):
     """router (nn.Linear hidden -> E), gate_up (E experts, hidden -> 2 * intermediate) and down (E experts, intermediate -> hidden).
     expert_mask (bool [E], optional): the experts this instance owns; the slots of the others are skipped (their o rows are zero), which
@@ -42,15 +49,15 @@ class MXFP4MoECuda(nn.Module):
     def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, bias: bool = True, swiglu_limit: float = 7.0,
                  swiglu_alpha: float = 1.702, device: torch.device = None, dtype: torch.dtype = torch.bfloat16, activations: str = "dtype") -> None:
         super().__init__()
-        if activations not in ("dtype", "mxfp4"):
-            raise ValueError(f"mxfp4 moe: activations must be 'dtype' or 'mxfp4' (got {activations!r})")
+        if not isinstance(activations, str) or activations not in _EXPERTS:
+            raise ValueError(f"mxfp4 moe: activations must be 'dtype', 'mxfp4' or 'mxfp8' (got {activations!r})")
         if not 1 <= top_k <= min(num_experts, 32):
             raise ValueError(f"mxfp4 moe needs 1 <= top_k <= min(num_experts, 32) (got top_k={top_k}, num_experts={num_experts})")
         self.hidden, self.intermediate, self.num_experts, self.top_k = hidden, intermediate, num_experts, top_k
         self.swiglu_limit, self.swiglu_alpha, self.dtype = float(swiglu_limit), float(swiglu_alpha), dtype
         self.router = nn.Linear(hidden, num_experts, bias=bias, device=device, dtype=dtype)
         self.activations = activations
-        experts = MXFP4A4ExpertsLinearCuda if activations == "mxfp4" else MXFP4ExpertsLinearCuda
+        experts = _EXPERTS[activations]
         self.gate_up = experts(num_experts, hidden, 2 * intermediate, bias=bias, device=device, dtype=dtype)
         self.down = experts(num_experts, intermediate, hidden, bias=bias, device=device, dtype=dtype)
         self.register_buffer("expert_mask", None, persistent=False)

@@ -160,6 +160,17 @@ int mxfp4_moe_a4_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t
 int mxfp4_moe_a4_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                                 void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
 
+// mxfp4_moe_a8.hip
+int mxfp4_moe_a8_form(long P, long E, long N, long K, int dtype);
+bool mxfp4_moe_a8_decode_ok(long P);
+bool mxfp4_moe_a8_one_launch_ok(long K);
+size_t mxfp4_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form);
+int mxfp4_moe_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st);
+int mxfp4_moe_a8_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
+
 // mxfp4_moe.hip
 int mxfp4_moe_form(long P, long E, long N, long K, int dtype);
 bool mxfp4_moe_decode_ok(long P);
@@ -1151,7 +1162,8 @@ size_t bie_mxfp4_moe_a4_workspace_bytes(long T, long S, long E, long K, int x_pe
     return mxfp4_moe_a4_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
 }
 
-static int check_mx_moe_a4(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
+// The shape limits shared by the W4A4 and W4A8 expert entries.
+static int check_mx_moe_act(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form) {
     int rc = check_mx(fn, N, K);
     if (rc) return rc;
     BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
@@ -1163,7 +1175,14 @@ static int check_mx_moe_a4(const char* fn, long T, long S, long E, long N, long 
                 "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
     BIE_REQUIRE(x_per_pair == 0 || x_per_pair == 1, BIE_ERR_INVALID_ARG, "%s: x_per_pair %d (0 = x is [T, K], 1 = x is [P, K])", fn, x_per_pair);
     BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, *form);
+    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, form);
+    return BIE_OK;
+}
+
+static int check_mx_moe_a4(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
+    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
+    if (rc) return rc;
+    const long P = T * S;
     if (*form < 0) *form = mxfp4_moe_a4_form(P, E, N, K, dtype);
     BIE_REQUIRE(*form == 1 || mxfp4_moe_a4_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
     return BIE_OK;
@@ -1195,6 +1214,54 @@ int bie_mxfp4_moe_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* r
                     (form == 0 || !misaligned(workspace, 16)),
                 BIE_ERR_INVALID_ARG, "%s: xq, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
     return mxfp4_moe_a4_gemm_launch(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
+                                    as_stream(stream));
+}
+
+// ---- MXFP4 W4A8 mixture of experts.  Everything is checked here, before any device call; the shape limits are the W4A4 entries' (check_mx_moe_act).
+int bie_mxfp4_moe_a8_form(long P, long E, long N, long K, int dtype) { return mxfp4_moe_a8_form(P, E, N, K, dtype); }
+
+size_t bie_mxfp4_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
+    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
+    if (form == 0 && !mxfp4_moe_a8_decode_ok(T * S)) return 0;
+    return mxfp4_moe_a8_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
+}
+
+static int check_mx_moe_a8(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
+    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
+    if (rc) return rc;
+    const long P = T * S;
+    if (*form < 0) *form = mxfp4_moe_a8_form(P, E, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || mxfp4_moe_a8_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
+    return BIE_OK;
+}
+
+int bie_mxfp4_moe_a8_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                             void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    const char* fn = "bie_mxfp4_moe_a8_forward";
+    int rc = check_mx_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
+    if (rc) return rc;
+    const bool need_ws = form == 1 || !mxfp4_moe_a8_one_launch_ok(K);
+    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
+                    (!need_ws || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
+    return mxfp4_moe_a8_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+}
+
+int bie_mxfp4_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                          const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                          int dtype, int form, void* stream) {
+    const char* fn = "bie_mxfp4_moe_a8_gemm";
+    int rc = check_mx_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
+    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
+                    (form == 0 || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: xq, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
+    return mxfp4_moe_a8_gemm_launch(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
                                     as_stream(stream));
 }
 

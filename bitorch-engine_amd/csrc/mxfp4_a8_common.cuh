@@ -1,7 +1,7 @@
-// The device-side pieces of the W4A8 translation unit (mxfp4_a8.hip; gfx950) that a later kernel may want to share: the MXFP8 (E4M3)
-// activation quantiser's rule for one 8-value unit, so that a kernel that quantises a row itself produces the bits of
-// mxa8_quantize_kernel, and the prefill tile body on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP4 A operand and an E4M3 B operand
-// (mxa8_gemm_tile: mxa8_gemm_kernel of mxfp4_a8.hip; it takes the row sources of mxfp4_common.cuh like mxa4_gemm_tile).
+// The device-side pieces of the W4A8 translation units (mxfp4_a8.hip, mxfp4_moe_a8.hip; gfx950): the MXFP8 (E4M3)
+// activation quantiser's rule for one 8-value unit, so that a kernel that quantises a row itself (mxma8_decode_kernel) produces the
+// bits of mxa8_quantize_kernel, and the prefill tile body on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP4 A operand and an E4M3 B operand
+// (mxa8_gemm_tile: mxa8_gemm_kernel of mxfp4_a8.hip and mxma8_gemm_kernel of mxfp4_moe_a8.hip; it takes the row sources of mxfp4_common.cuh like mxa4_gemm_tile).
 #pragma once
 #include "mxfp4_a4_common.cuh"
 

@@ -1,0 +1,274 @@
+// MXFP4 W4A8 expert GEMM for gfx950: the stacked expert weights of mxfp4_moe.hip against activations quantised to MXFP8 (E4M3 elements,
+// E8M0 block scales) on the fly, contracted on the block-scaled matrix instructions with an FP4 A operand and an E4M3 B operand
+// (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A8 mixture-of-experts layer").  No reference implementation exists.
+//
+//   T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p]; row(p) = p / S (x_per_pair = 0) or p
+//   xq uint8 [R, K] (e4m3fn bytes) / xs uint8 [R, K/32] / row_flag uint8 [R]: the stored rows of x (R = T or P) by the rule of
+//   mxa8_quantize_kernel (mxfp4_a8.hip)
+//   y[p, n] = dt( sum_b 2^(xs[row(p), b] + scales[e, n, b] - 254) * (sum_{k in b} e4m3(xq) * e2m1(qweight)) + bias[e, n] ),  e = idx[p]
+//   y[p, :] = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255; y[p, :] = +0 where idx[p] is outside [0, E), whatever
+//   the row's flag: the index is compared before any address is formed from it
+//
+// A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
+// row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
+//
+// Routed decode form (mxma8_decode_kernel, P <= 1024): a workgroup per pair and strip of 16 C16 columns of its expert, K split over the
+// 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4 in the operand order of mxfp4_a8.hip (the only one
+// profiles/mxfp4_a8_probe.txt pinned): the weight fragment is A (FP4, cbsz 4), the x fragment B (E4M3, blgp 0, the two halves of
+// a8_frag), byte select 0.  The pair's row is column 0 of B, so the lanes with (lane & 15) == 0 carry it; all other columns are zero
+// codes under scale code 127.  The four partial sums meet in LDS and are summed as ((w0 + w1) + w2) + w3, the order of
+// mxa8_decode_kernel: a pair's row has the bits of the dense W4A8 decode form.  FUSED (one launch, K <= MXMA8_ONE_K): the workgroup
+// quantises x_row(p) into LDS itself (a8_quantize_unit, the bits of mxa8_quantize_kernel; codes, scale bytes, and the non-finite flag
+// through the barrier) and reads neither xq nor a workspace.  Not FUSED: it reads xq / xs / row_flag from memory.
+// Grouped prefill form: mxa8_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
+// mxma8_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mxa8_gemm_tile (mxfp4_a8_common.cuh) at 128 x 128.  A row tile belongs to one
+// expert, gathers the xq / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the segment enter
+// as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no
+// K loop and store zeros.
+#include "mxfp4_a8_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// mxfp4_a8.hip, mxfp4_moe.hip
+int mxfp4_a8_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
+size_t mxfp4_moe_workspace_bytes(long P, long E);
+long mxfp4_moe_max_tiles(long P, long E);
+int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
+
+// ---- routed decode form -------------------------------------------------------------------------------------------------------------------
+// The largest K of the one-launch form: a row's image in LDS is K bytes of codes and K / 32 scale bytes (16896 bytes at the bound, the
+// footprint class of the W4A4 kernel's 17408, whose occupancy is the measured one).
+constexpr int MXMA8_ONE_K = 16384;
+constexpr int MXMA8_DECODE_PAIRS = 1024;  // the grid's second dimension
+
+// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
+// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step's weights; the lanes
+// with (l & 15) == 0 hold the x bytes 16 (l >> 4) .. + 15 and 64 + 16 (l >> 4) .. + 15 of the step and the x scale of block l >> 4.
+// xin is x (FUSED) or xq.
+template <int DT, int C16, bool FUSED>
+__global__ __launch_bounds__(256) void mxma8_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                           const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                           const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                           int N, int K, int x_per_pair) {
+    constexpr int C = 16 * C16;
+    __shared__ float red[4][C];
+    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MXMA8_ONE_K + MXMA8_ONE_K / 32 : 16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int p = blockIdx.y, n0 = blockIdx.x * C;
+    const int e = idx[p];
+    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
+        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
+        return;
+    }
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const long xrow = x_per_pair ? p : p / S;
+    const uint8_t* xqr = nullptr;
+    const uint8_t* xsr = nullptr;
+    int flagged;
+    if constexpr (FUSED) {
+        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
+        const int U = K >> 3;  // a multiple of 4: whole quads are in or out
+        int bad = 0;
+        for (int u = t; u < U; u += 256) {
+            uint2_t codes;
+            uint32_t scode;
+            a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
+            reinterpret_cast<uint2_t*>(img)[u] = codes;
+            if ((u & 3) == 0) img[K + (u >> 2)] = (unsigned char)scode;
+        }
+        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
+    } else {
+        xqr = reinterpret_cast<const uint8_t*>(xin) + xrow * K;
+        xsr = xs + xrow * KB;
+        flagged = row_flag[xrow];
+    }
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+    const uint8_t* wrow[C16];
+    const uint8_t* srow[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) {
+        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
+        wrow[c] = qw + n * (K >> 1);
+        srow[c] = sc + n * KB;
+    }
+    mxa4_v4f acc[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t w[C16];
+        int sw[C16];
+#pragma unroll
+        for (int c = 0; c < C16; c++) {
+            w[c] = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow[c]) + kc);
+            sw[c] = __builtin_nontemporal_load(srow[c] + kc);
+        }
+        // this lane's x halves: 16 bytes of block kq >> 1 of the step and 16 bytes of that block + 2, at offset 16 (kq & 1) in each
+        const int kb0 = s * 4 + (kq >> 1), kb1 = kb0 + 2;
+        uint4_t a0 = uint4_t{0u, 0u, 0u, 0u}, a1 = uint4_t{0u, 0u, 0u, 0u};
+        int sa = 127;
+        if (r16 == 0) {
+            const int o0 = kb0 * 32 + (kq & 1) * 16, o1 = kb1 * 32 + (kq & 1) * 16;
+            if constexpr (FUSED) {
+                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(img + o0);
+                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(img + o1);
+                if (kin) sa = img[K + kb];
+            } else {
+                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(xqr + o0);
+                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(xqr + o1);
+                if (kin) sa = xsr[kb];
+            }
+        }
+        if (!kin) {
+#pragma unroll
+            for (int c = 0; c < C16; c++) {
+                w[c] = uint4_t{0u, 0u, 0u, 0u};
+                sw[c] = 127;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C16; c++)
+            acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(w[c]), a8_frag(a0, a1), acc[c], 4, 0, 0, sw[c], 0, sa);
+    }
+    // C/D: D column (= row of the x operand) = lane & 15, D row (= column n of the strip) = 4 (lane >> 4) + r: the pair's row is
+    // registers 0 .. 3 of lanes 0, 16, 32, 48
+    if (r16 == 0) {
+#pragma unroll
+        for (int c = 0; c < C16; c++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) red[wave][c * 16 + 4 * kq + r] = acc[c][r];
+    }
+    __syncthreads();
+    if (t < C) {
+        const int n = n0 + t;
+        if (n < N) {
+            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
+            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
+            dt_traits<DT>::store(y, (long)p * N + n, v);
+        }
+    }
+}
+
+// ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
+constexpr int MXMA8_W = 2;  // WM = WN of the tile: 128 x 128
+static_assert(64 * MXMA8_W == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
+
+// A workgroup per (row tile of the table, column tile): mxa8_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+template <int DT>
+__global__ __launch_bounds__(256) void mxma8_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                         const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                         const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                         int N, int K, int x_per_pair, int max_tiles) {
+    __shared__ int prow[MXM_BM];
+    int e, n0;
+    if (!mxm_tile_begin<DT, 64 * MXMA8_W>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
+    mxa8_gemm_tile<DT, MXMA8_W, MXMA8_W>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The routed decode form exists for P <= MXMA8_DECODE_PAIRS.  The plan's bound was measured (tools/mxfp4_moe_a8_bench.py,
+// profiles/mxfp4_moe_a8_bench.jsonl, the `sweep` rows: both gpt-oss-20b projections at E = 32 and E = 128, fp16 and bf16, both forms
+// forced at P = 1, 2, 4, ..., 1024, graph time, routings and weight stacks rotated; fp16 and bf16 agree within 4 % but for the
+// decode rows at E = 128, P <= 16 (5 - 11 %) and one grouped row (12 %): no verdict below turns on that).  The decode form streams an expert's weights once per pair and grows linearly in P (7.5 / 15.2 / 47 / 90 / 175 / 349 us at
+// P = 1 / 4 / 16 / 32 / 64 / 128 on 2880 -> 5760); the grouped form costs 41 us at P = 1 (three launches, one row tile walking K) and
+// then grows with the number of experts that hold a pair.  At E = 32 the decode form led at every P <= 32 (P = 32: 90 against 143 - 148
+// us at 5760, 46 against 79 at 2880); P = 64 was split (175 against 165 at 5760, 88 against 99 - 101 at 2880) and the grouped form led
+// from P = 128 on (349 against 168, 173 against 108 - 110).  At E = 128, where nearly every pair of a small call has an expert of its
+// own, the decode form led through P = 128 (P = 64: 177 against 267, 91 against 158; P = 128: 355 against 426 - 432, 179 against 221)
+// and the grouped form from P = 256 on (713 against 538 - 553, 352 against 312).  So the plan takes the decode form for P <= 32, and up
+// to P = 128 while P <= E.  The second bound is wider than the W4A4 layer's (64 while 2 P <= E) because this layer's grouped form is the
+// slower of the two (the `accept` rows: 1.07 - 1.48 x the W4A4 grouped form's time) while its decode form is the faster.  E between 32
+// and 128 and beyond 128, and P between the powers of two, were not measured: the second clause extends the E = 128 rows by the
+// pairs-per-expert argument.  (The rows' `plan` column is the plan of the build that measured them, the W4A4 constants 32 / 64 / 2 P <= E,
+// which these rows replaced; the `accept` rows ran P = 4, 64, 1024 and 16384 at E = 32, where both plans choose alike.)
+// The strip width of the decode form: 16, 32 and 64 columns per workgroup measured at P = 1, 4, 16, 64 on both projections (the `strip`
+// rows): 16 columns were ahead or level (within 1 %) on every row (P = 1: 7.2 / 7.7 / 10.6 us at 5760; P = 64: 175 / 183 / 198).
+constexpr int MXMA8_PLAN_PAIRS = 32, MXMA8_PLAN_PAIRS_SPARSE = 128;
+constexpr int MXMA8_STRIP = 1;  // C16 of the decode form: strips of 16 columns (BIE_MXFP4_MOE_A8_STRIP = 1 / 2 / 4 under BIE_TUNING)
+
+bool mxfp4_moe_a8_decode_ok(long P) { return P >= 1 && P <= MXMA8_DECODE_PAIRS; }
+bool mxfp4_moe_a8_one_launch_ok(long K) { return K <= MXMA8_ONE_K; }
+
+int mxfp4_moe_a8_form(long P, long E, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_MOE_A8_FORM", -1);
+    if (f == 0 && P <= MXMA8_DECODE_PAIRS) return 0;
+    if (f == 1) return 1;
+    return (P <= MXMA8_PLAN_PAIRS || (P <= MXMA8_PLAN_PAIRS_SPARSE && P <= E)) ? 0 : 1;
+}
+
+// Workspace of bie_mxfp4_moe_a8_forward, every region 16-byte aligned: xq [R, K], xs [R, K/32], row_flag [R] for the R stored rows of
+// x (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip.
+static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
+static long a8m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
+static size_t a8m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)K); }
+static size_t a8m_flag_offset(long R, long K) { return a8m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
+static size_t a8m_route_offset(long R, long K) { return a8m_flag_offset(R, K) + al16((size_t)R); }
+
+size_t mxfp4_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    return a8m_route_offset(a8m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+}
+
+template <int DT, int C16, bool FUSED>
+static void a8m_decode_launch_t(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                                const uint8_t* ecol, const void* bias, void* y, long P, int S, int E, int N, int K, int xpp, hipStream_t st) {
+    const dim3 grid((unsigned)cdivl(N, 16 * C16), (unsigned)P);
+    hipLaunchKernelGGL((mxma8_decode_kernel<DT, C16, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, S, E, N, K, xpp);
+}
+
+template <int DT, bool FUSED>
+static int a8m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
+    const int strip = BIE_KNOB("BIE_MXFP4_MOE_A8_STRIP", MXMA8_STRIP);
+    if (strip >= 4) a8m_decode_launch_t<DT, 4, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else if (strip >= 2) a8m_decode_launch_t<DT, 2, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else a8m_decode_launch_t<DT, 1, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    return check_launch("mxma8_decode_kernel");
+}
+
+// The contraction from quantised activations.  form 0: the routed kernel reading xq from memory (no workspace); form 1: routing into the
+// workspace (the routing region alone), then the grouped GEMM.
+int mxfp4_moe_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st) {
+    const long P = T * S;
+    if (form == 0) {
+        if (dtype == BIE_F16) return a8m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a8m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
+    if (rc) return rc;
+    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
+    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * MXMA8_W)));
+    if (dtype == BIE_F16)
+        hipLaunchKernelGGL(mxma8_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    else
+        hipLaunchKernelGGL(mxma8_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    return check_launch("mxma8_gemm_kernel");
+}
+
+// The whole layer from x.  form 0 with K <= MXMA8_ONE_K: one launch, the workspace is not touched.
+int mxfp4_moe_a8_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
+    const long P = T * S, R = a8m_rows(T, S, x_per_pair);
+    if (form == 0 && K <= MXMA8_ONE_K) {
+        if (dtype == BIE_F16) return a8m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a8m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a8m_xs_offset(R, K);
+    uint8_t* rf = xq + a8m_flag_offset(R, K);
+    const int rc = mxfp4_a8_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_moe_a8_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a8m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+}
+
+}  // namespace bie
