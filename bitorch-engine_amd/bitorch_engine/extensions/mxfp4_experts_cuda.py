@@ -5,8 +5,9 @@ library's own (include/bie_hip.h, INTEGRATION.md "MXFP4 mixture-of-experts layer
   idx int32 [T, S]: the expert of every (token, slot) pair; an index outside [0, E) (-1 by convention) is a skipped slot
   y[t, s] = dt( x_row . W[idx[t, s]]^T + bias[idx[t, s]] ),  0 for a skipped slot;   x_row = x[t] (x [T, K]) or x[t, s] (x [T, S, K])
 
-quantize / dequant / col_exp are mxfp4_linear_cuda's on the [E * N, K] view.  Nothing here synchronises with the host (the routing is
-read on the device), so every entry can be captured in a graph."""
+quantize / dequant / col_exp are mxfp4_linear_cuda's on the [E * N, K] view.  grad_input is the backward's gx[p] = gy[p] . W[idx[p]] on
+the packed weights (csrc/mxfp4_grad.hip), rebiased by blk_exp's per-expert, per-block-column largest scale code.  Nothing here
+synchronises with the host (the routing is read on the device), so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip
@@ -79,3 +80,50 @@ def forward(x: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: t
     _hip.check(L.bie_mxfp4_moe_forward(_hip.ptr(x), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y),
                                        _hip.ptr(ws), T, S, E, N, K, x_per_pair, _hip.dt(x), int(form), _hip.stream()), "bie_mxfp4_moe_forward")
     return y
+
+
+def blk_exp(scales: torch.Tensor) -> torch.Tensor:
+    """e_blk uint8 [E, K/32]: the largest scale code of each expert's block-column over its N rows (255 where it has a NaN block)."""
+    _hip.need_gpu(scales)
+    if scales.dtype != torch.uint8 or scales.dim() != 3:
+        raise RuntimeError("mxfp4 experts: scales must be uint8 [E, N, K/32]")
+    E, N, KB = scales.shape
+    e = torch.empty((E, KB), dtype=torch.uint8, device=scales.device)
+    scales = scales.contiguous()
+    _hip.check(_hip.lib().bie_mxfp4_blk_exp(_hip.ptr(scales), _hip.ptr(e), N, KB * 32, E, _hip.stream()), "bie_mxfp4_blk_exp")
+    return e
+
+
+def grad_input(gy: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None,
+               out_dtype: torch.dtype = None) -> torch.Tensor:
+    """gy [T, S, N] or [P, N] (fp16 / bf16, any N), idx int32 [T, S] -> gx [P, K], gx[p] = gy[p] . W[idx[p]] (0 for a skipped slot), in
+    gy's dtype or, with out_dtype=torch.float32, in fp32 (the caller sums a token's slots before the one rounding).  No image of W is
+    built.  e_blk (blk_exp(scales)) is computed here when it is not given."""
+    _hip.need_gpu(gy, idx, qweight, scales, e_blk)
+    if gy.dtype not in _X_DT:
+        raise RuntimeError(f"mxfp4 experts grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
+    if out_dtype is None:
+        out_dtype = gy.dtype
+    if out_dtype not in (gy.dtype, torch.float32):
+        raise RuntimeError(f"mxfp4 experts grad_input: out_dtype {out_dtype} must be gy's dtype or float32")
+    E, N, K = _shape(qweight, scales)
+    if idx.dtype != torch.int32 or idx.dim() != 2:
+        raise RuntimeError(f"mxfp4 experts: idx must be int32 [T, S] (got {idx.dtype} {tuple(idx.shape)})")
+    T, S = idx.shape
+    P = T * S
+    if tuple(gy.shape) not in ((T, S, N), (P, N)):
+        raise RuntimeError(f"mxfp4 experts grad_input: gy {tuple(gy.shape)} does not match idx {tuple(idx.shape)} and N={N}")
+    gx = torch.empty((P, K), dtype=out_dtype, device=gy.device)
+    if P == 0:
+        return gx
+    L = _hip.lib()
+    if e_blk is None:
+        e_blk = blk_exp(scales)
+    elif e_blk.dtype != torch.uint8 or tuple(e_blk.shape) != (E, K // 32):
+        raise RuntimeError(f"mxfp4 experts grad_input: e_blk must be uint8 [E = {E}, K/32 = {K // 32}]")
+    ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(P, E)), dtype=torch.uint8, device=gy.device)
+    gy, idx, qweight, scales, e_blk = gy.contiguous(), idx.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()
+    _hip.check(L.bie_mxfp4_moe_grad_input(_hip.ptr(gy), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), _hip.ptr(ws),
+                                          T, S, E, N, K, _hip.dt(gy), int(out_dtype == torch.float32), _hip.stream()),
+               "bie_mxfp4_moe_grad_input")
+    return gx

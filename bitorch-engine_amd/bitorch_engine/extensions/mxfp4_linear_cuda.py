@@ -5,8 +5,9 @@ the arithmetic are this library's own (include/bie_hip.h, INTEGRATION.md "MXFP4 
   W[n, k] = e2m1(code) * 2^(s - 127)                                   y = dt( x . W^T + bias )  (fp32 sums, one rounding)
 
 quantize / dequant convert between a float weight and the packed pair, col_exp gives the per-row largest scale code the prefill form
-rebiases by, forward runs the layer (the form from bie_mxfp4_form unless one is given).  Nothing here synchronises with the host, so
-every entry can be captured in a graph."""
+rebiases by, forward runs the layer (the form from bie_mxfp4_form unless one is given).  grad_input is the backward's gx = gy . W on
+the packed weight (csrc/mxfp4_grad.hip), rebiased by blk_exp's per-block-column largest scale code.  Nothing here synchronises with
+the host, so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip
@@ -88,3 +89,38 @@ def forward(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: 
     _hip.check(_hip.lib().bie_mxfp4_linear_forward(_hip.ptr(x), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y), M, N, K,
                                                    _hip.dt(x), int(form), _hip.stream()), "bie_mxfp4_linear_forward")
     return y
+
+
+def blk_exp(scales: torch.Tensor) -> torch.Tensor:
+    """e_blk uint8 [K/32]: the largest scale code of each block-column over the N rows (255 where a block-column has a NaN block)."""
+    _hip.need_gpu(scales)
+    if scales.dtype != torch.uint8 or scales.dim() != 2:
+        raise RuntimeError("mxfp4: scales must be uint8 [N, K/32]")
+    N, KB = scales.shape
+    e = torch.empty(KB, dtype=torch.uint8, device=scales.device)
+    scales = scales.contiguous()
+    _hip.check(_hip.lib().bie_mxfp4_blk_exp(_hip.ptr(scales), _hip.ptr(e), N, KB * 32, 1, _hip.stream()), "bie_mxfp4_blk_exp")
+    return e
+
+
+def grad_input(gy: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None) -> torch.Tensor:
+    """gy [M, N] (fp16 / bf16, any N) -> gx = gy . W [M, K] in gy's dtype, from the packed weight: no image of W is built.  e_blk
+    (blk_exp(scales)) is computed here when it is not given."""
+    _hip.need_gpu(gy, qweight, scales, e_blk)
+    if gy.dtype not in _X_DT:
+        raise RuntimeError(f"mxfp4 grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
+    N, K = _shape(qweight, scales)
+    if gy.dim() != 2 or gy.shape[1] != N:
+        raise RuntimeError(f"mxfp4 grad_input: gy {tuple(gy.shape)} does not match N={N}")
+    M = gy.shape[0]
+    gx = torch.empty((M, K), dtype=gy.dtype, device=gy.device)
+    if M == 0:
+        return gx
+    if e_blk is None:
+        e_blk = blk_exp(scales)
+    elif e_blk.dtype != torch.uint8 or e_blk.numel() != K // 32:
+        raise RuntimeError(f"mxfp4 grad_input: e_blk must be uint8 [K/32 = {K // 32}]")
+    gy, qweight, scales, e_blk = gy.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()  # held until the launch is queued
+    _hip.check(_hip.lib().bie_mxfp4_linear_grad_input(_hip.ptr(gy), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), M, N, K,
+                                                      _hip.dt(gy), _hip.stream()), "bie_mxfp4_linear_grad_input")
+    return gx

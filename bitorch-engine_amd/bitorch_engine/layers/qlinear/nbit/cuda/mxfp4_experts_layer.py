@@ -10,7 +10,9 @@ MXFP4 checkpoints (set_mx_weight).  e_col is derived from scales and not saved.
 
 Training (train() with the latent weight): re-quantised on every call, the forward runs on the kernels and the backward is the
 straight-through composition in torch, expert by expert.  Eval: the packed weight; a forward with grad enabled is differentiable in x
-(and bias)."""
+(and bias).  grad_input="kernel" takes grad_x from the packed weights in one grouped call (csrc/mxfp4_grad.hip: nothing is
+dequantised, and with frozen weights and no bias gradient the backward has no expert loop and no host synchronisation), in train()
+and in eval(); the default "torch" dequantises all experts to fp32 and loops."""
 import math
 import typing
 
@@ -29,11 +31,14 @@ class MXFP4ExpertsLinearForward(Function):
       grad_x[row(p)] += gy[p] . W[e]        (summed over a token's slots when x is [T, K])
       grad_weight[e]  = gy[pairs of e]^T . x_rows
       grad_bias[e]    = sum gy[pairs of e]
-    Skipped slots contribute nothing.  A loop over the experts in torch: not a hot path."""
+    Skipped slots contribute nothing.  A loop over the experts in torch: not a hot path.  With kernel=True grad_x is one call of
+    mxfp4_experts_cuda.grad_input on the packed weights (e_blk from the scales of this call; fp32 rows summed over a token's slots and
+    rounded once when x is [T, K]), and the loop runs for grad_weight / grad_bias only."""
 
     @staticmethod
-    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, idx, qweight, scales)
+        ctx.kernel = kernel
         return mxfp4_experts_cuda.forward(x, idx, qweight, scales, bias, e_col)
 
     @staticmethod
@@ -43,6 +48,15 @@ class MXFP4ExpertsLinearForward(Function):
         E, N, K = qweight.shape[0], qweight.shape[1], qweight.shape[2] * 2
         T, S = idx.shape
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gxk = None
+        if need_x and ctx.kernel:
+            if x.dim() == 3:
+                gxk = mxfp4_experts_cuda.grad_input(gy, idx, qweight, scales).reshape(T, S, K)
+            else:
+                gxk = mxfp4_experts_cuda.grad_input(gy, idx, qweight, scales, out_dtype=torch.float32).reshape(T, S, K).sum(1).to(gy.dtype)
+            need_x = False
+            if not (need_w or need_b):
+                return gxk, None, None, None, None, None, None, None
         g = gy.reshape(T * S, N).float()
         flat = idx.reshape(-1).long()
         xr = (x if x.dim() == 3 else x[:, None, :].expand(T, S, K)).reshape(T * S, K).float()
@@ -63,17 +77,23 @@ class MXFP4ExpertsLinearForward(Function):
                 gb[e] = ge.sum(0)
         if need_x:
             gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
-        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
+        elif gxk is not None:
+            gx = gxk
+        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None, None
 
 
 class MXFP4ExpertsLinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [E, N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight),
     the packed codes `qweight` uint8 [E, N, K/2] and E8M0 `scales` uint8 [E, N, K/32] (buffers), an optional `bias` [E, N].
-    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16."""
+    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16.  grad_input: "torch" (the backward's grad_x from an fp32 image of every
+    expert's W, expert by expert) or "kernel" (one grouped call on the packed weights)."""
 
     def __init__(self, num_experts: int, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
-                 dtype: torch.dtype = torch.float16) -> None:
+                 dtype: torch.dtype = torch.float16, grad_input: str = "torch") -> None:
         super().__init__()
+        if grad_input not in ("torch", "kernel"):
+            raise ValueError(f'grad_input must be "torch" or "kernel" (got {grad_input!r})')
+        self.grad_input = grad_input
         if input_features % 32 or input_features <= 0 or input_features > (1 << 20) or out_features <= 0 or not 1 <= num_experts <= 1024:
             raise ValueError(f"mxfp4 experts need input_features % 32 == 0, 32 <= input_features <= 2^20, out_features >= 1 and "
                              f"1 <= num_experts <= 1024 (got {input_features}, {out_features}, {num_experts})")
@@ -143,4 +163,5 @@ class MXFP4ExpertsLinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return mxfp4_experts_cuda.forward(x, idx, qweight, scales, self.bias, e_col)
-        return MXFP4ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col)
+        return MXFP4ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col,
+                                               self.grad_input == "kernel")

@@ -7,7 +7,8 @@ qweight uint8 [N, K/2] and scales uint8 [N, K/32] are byte for byte the `blocks`
 
 Training (train() with the latent weight): re-quantised on every call by the OCP MX rule, the forward runs on the kernels and the
 backward is the straight-through composition in torch.  Eval: the packed qweight / scales; a forward with grad enabled is
-differentiable in x (and bias)."""
+differentiable in x (and bias).  grad_input="kernel" takes grad_x from the packed weight instead (csrc/mxfp4_grad.hip: no float image
+of W is built), in train() and in eval(); the default "torch" dequantises W to fp32 and multiplies."""
 import math
 import typing
 
@@ -24,13 +25,14 @@ mxfp4_linear_cuda = import_extension("mxfp4_linear_cuda")
 
 class MXFP4LinearForward(Function):
     """Forward: the layer kernels.  Backward (straight-through estimator, in fp32, cast to the dtype):
-      grad_x      = gy . W
+      grad_x      = gy . W            (kernel: mxfp4_linear_cuda.grad_input on the packed weight, e_blk from the scales of this call)
       grad_weight = gy^T . x          (the float latent weight, as if it were W)
       grad_bias   = sum_m gy"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, qweight, scales)
+        ctx.kernel = kernel
         return mxfp4_linear_cuda.forward(x, qweight, scales, bias, e_col)
 
     @staticmethod
@@ -39,22 +41,29 @@ class MXFP4LinearForward(Function):
         x, qweight, scales = ctx.saved_tensors
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
-            grad_x = gy.float().mm(mxfp4_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
+            if ctx.kernel:
+                grad_x = mxfp4_linear_cuda.grad_input(gy, qweight, scales)
+            else:
+                grad_x = gy.float().mm(mxfp4_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
         if ctx.needs_input_grad[1]:
             grad_w = gy.float().t().mm(x.float()).to(gy.dtype)
         if ctx.needs_input_grad[2]:
             grad_b = gy.float().sum(0).to(gy.dtype)
-        return grad_x, grad_w, grad_b, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None
 
 
 class MXFP4LinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight),
     the packed codes `qweight` uint8 [N, K/2] and E8M0 `scales` uint8 [N, K/32] (buffers), an optional `bias` [N].
-    K % 32 == 0, K <= 2^20; dtype fp16 or bf16."""
+    K % 32 == 0, K <= 2^20; dtype fp16 or bf16.  grad_input: "torch" (the backward's grad_x from an fp32 image of W) or "kernel" (from
+    the packed weight)."""
 
     def __init__(self, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
-                 dtype: torch.dtype = torch.float16) -> None:
+                 dtype: torch.dtype = torch.float16, grad_input: str = "torch") -> None:
         super().__init__()
+        if grad_input not in ("torch", "kernel"):
+            raise ValueError(f'grad_input must be "torch" or "kernel" (got {grad_input!r})')
+        self.grad_input = grad_input
         if input_features % 32 or input_features <= 0 or input_features > (1 << 20) or out_features <= 0:
             raise ValueError(f"mxfp4 linear needs input_features % 32 == 0, 32 <= input_features <= 2^20 and out_features >= 1 "
                              f"(got {input_features}, {out_features})")
@@ -120,5 +129,5 @@ class MXFP4LinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return unflatten_x(mxfp4_linear_cuda.forward(x2, qweight, scales, self.bias, e_col), lead)
-        out = MXFP4LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col)
+        out = MXFP4LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel")
         return unflatten_x(out, lead)

@@ -1,7 +1,8 @@
 // The MXFP4 format's device-side rules and everything the MXFP4 translation units share (gfx950): E8M0 scale codes to fp32, the
 // quantiser's rounding and block-scale rules, the fp4 -> fp16 / bf16 converts with their dot2 and MFMA, the fp32 wave sum on the DPP
 // network, the row sources of the tile GEMMs, the weight-only 128 x 128 tile body (mx_gemm_tile: mx_gemm_kernel of mxfp4.hip and
-// mxm_gemm_kernel of mxfp4_moe.hip), and the routing workspace of the grouped expert GEMMs with their common prologue (mxm_tile_begin).
+// mxm_gemm_kernel of mxfp4_moe.hip), the input-gradient 128 x 128 tile body (mx_dgrad_tile: the kernels of mxfp4_grad.hip), and the
+// routing workspace of the grouped expert GEMMs with their common prologue (mxm_tile_begin).
 #pragma once
 #include "mfma_pipe.cuh"
 
@@ -227,6 +228,175 @@ __device__ __forceinline__ void mx_gemm_tile(const Rows& rows, const uint16_t* _
                 }
             }
     }
+}
+
+// ---- the input-gradient tile -----------------------------------------------------------------------------------------------------------------
+constexpr int MX_DG_BM = 128, MX_DG_BK = 128, MX_DG_BN = 64;  // rows of gy, columns k of gx, contraction rows n of a stage
+constexpr int MX_DG_APITCH = MX_DG_BN * 2 + 16;               // bytes per gy row in LDS (MX_APITCH's pad)
+constexpr int MX_DG_BPITCH = MX_DG_BN + 8;  // bytes per byte-column of codes: 64 n + 8 (18 dwords: the 8-byte reads of 32 lanes on distinct bank pairs)
+constexpr int MX_DG_SPITCH = MX_DG_BN + 4;  // fp32 per block-column of rebiased scales: 64 n + 4 (the two block-columns a half-wave reads on distinct banks)
+constexpr int MX_DG_STAGE = MX_DG_BM * MX_DG_APITCH + (MX_DG_BK / 2) * MX_DG_BPITCH + (MX_DG_BK / 32) * MX_DG_SPITCH * 4;
+
+// Eight code bytes of one byte column (rows n .. n + 7, byte j of w0 / w1) at their rows' rebiased scales -> the 8-n fragments of the
+// bytes' low nibbles (column 2 c) and high nibbles (column 2 c + 1): one convert per byte, the halves regrouped.
+template <int DT> struct mx_cvt2;
+template <> struct mx_cvt2<BIE_BF16> {
+    typedef bf16x2_t t;
+    template <int SEL>
+    static __device__ __forceinline__ t cvt(uint32_t w, float s) { return __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, SEL); }
+};
+template <> struct mx_cvt2<BIE_F16> {
+    typedef half2_t t;
+    template <int SEL>
+    static __device__ __forceinline__ t cvt(uint32_t w, float s) { return __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, SEL); }
+};
+template <int DT>
+__device__ __forceinline__ void mx_frag_columns(uint32_t w0, uint32_t w1, const float4_t& s0, const float4_t& s1, typename mx_frag<DT>::t& lo,
+                                                typename mx_frag<DT>::t& hi) {
+    typedef mx_cvt2<DT> C;
+    const typename C::t v0 = C::template cvt<0>(w0, s0[0]), v1 = C::template cvt<1>(w0, s0[1]);
+    const typename C::t v2 = C::template cvt<2>(w0, s0[2]), v3 = C::template cvt<3>(w0, s0[3]);
+    const typename C::t v4 = C::template cvt<0>(w1, s1[0]), v5 = C::template cvt<1>(w1, s1[1]);
+    const typename C::t v6 = C::template cvt<2>(w1, s1[2]), v7 = C::template cvt<3>(w1, s1[3]);
+    lo = typename mx_frag<DT>::t{v0[0], v1[0], v2[0], v3[0], v4[0], v5[0], v6[0], v7[0]};
+    hi = typename mx_frag<DT>::t{v0[1], v1[1], v2[1], v3[1], v4[1], v5[1], v6[1], v7[1]};
+}
+
+// two adjacent output columns (i even) in one store
+template <int ODT>
+__device__ __forceinline__ void mx_store2(void* p, long i, float v0, float v1) {
+    if constexpr (ODT == BIE_F32) *reinterpret_cast<float2_t*>(reinterpret_cast<float*>(p) + i) = float2_t{v0, v1};
+    else if constexpr (ODT == BIE_BF16) reinterpret_cast<uint32_t*>(p)[i >> 1] = pack_bf16x2(v0, v1);
+    else reinterpret_cast<uint32_t*>(p)[i >> 1] = f32_to_f16_bits(v0) | (f32_to_f16_bits(v1) << 16);
+}
+
+// One 128 x 128 tile of gx = gy . W on v_mfma_f32_32x32x16_{bf16,f16}, contracted over the N weight rows that start at row r0 of qw / sc
+// (0, or (long)e * N for expert e): tile rows from `rows` (a live row reads gy[src] and writes gx[dst]), columns k0 .. of K, rebiased by
+// eblk[k / 32] (the caller's pointer already at the expert's K / 32 codes).  ODT, the element type of gx, is DT or BIE_F32.  4 waves as
+// 2 x 2, wave tile 64 x 64.  Per stage of 64 n a thread loads 4 x 16 bytes of gy, four dwords of codes (rows 4 n4 .. + 3, byte columns
+// 4 d .. + 3) and one scale byte into registers while the MFMAs run on the other LDS buffer, then writes them: the codes TRANSPOSED
+// (a 4 x 4 byte transpose in registers; LDS holds [byte column][n]) and the scale rebiased to fp32 as [block-column][n].  Lane
+// (r = lane & 31, h = lane >> 5) of a 16-n step then reads the 8 bytes of byte column r, rows 8 h .. + 7, in one ds_read_b64 and their 8
+// scales in two ds_read_b128; each byte is one convert at its row's scale (a byte = the adjacent output columns 2 r, 2 r + 1); the 8
+// low halves and the 8 high halves are the B fragments of two MFMAs whose output column for lane r is k0 + 2 r and k0 + 2 r + 1, so the
+// epilogue stores two adjacent columns per lane.  gy rows have any length N: whole 16-byte pieces where `vec` (N % 8 == 0 and gy
+// 16-byte aligned), else 16-bit loads, each guarded by n < N.  Dead rows and whatever lies past N / K: gy and codes load as zero,
+// scales as 1.0, so the padding adds exact zeros.  All 256 threads of the workgroup must call it together.
+template <int DT, int ODT, class Rows>
+__device__ __forceinline__ void mx_dgrad_tile(const Rows& rows, const uint16_t* __restrict__ gy, const uint8_t* __restrict__ qw,
+                                              const uint8_t* __restrict__ sc, const uint8_t* __restrict__ eblk, void* __restrict__ gx, long r0,
+                                              int k0, int N, int K, bool vec) {
+    typedef mx_frag<DT> F;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX_DG_STAGE];
+    constexpr int B_OFF = MX_DG_BM * MX_DG_APITCH, S_OFF = B_OFF + (MX_DG_BK / 2) * MX_DG_BPITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int NT = (N + MX_DG_BN - 1) / MX_DG_BN, KB = K >> 5, KH = K >> 1;
+
+    // this thread's load slots
+    const int bd = t & 15, bn4 = t >> 4;  // codes: dword bd of the tile's 64 byte columns, rows 4 bn4 .. + 3 of the stage
+    const bool bk_ok = (k0 >> 1) + bd * 4 < KH;
+    const uint8_t* wsrc = qw + r0 * KH + (k0 >> 1) + bd * 4;
+    const int sn = t >> 2, sb = t & 3;  // scale: row sn of the stage, block-column sb of the tile
+    const bool sb_ok = (k0 >> 5) + sb < KB;
+    const uint8_t* ssrc = sc + r0 * KB + (k0 >> 5) + sb;
+    const uint32_t eb = sb_ok ? eblk[(k0 >> 5) + sb] : 0u;
+    const uint16_t* grow[4];  // the gy rows of this thread's four 16-byte pieces per stage: tile row (t + 256 i) / 8, piece t & 7
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = (t + 256 * i) >> 3;
+        grow[i] = rows.live(row) ? gy + rows.src(row) * N : nullptr;
+    }
+    uint4_t ra[4];
+    uint32_t rb[4];
+    float rs;
+    auto load = [&](int nt) {
+        const int na = nt * MX_DG_BN + (t & 7) * 8;  // the first n of this thread's pieces
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (!grow[i] || na >= N) {
+                ra[i] = uint4_t{0u, 0u, 0u, 0u};
+            } else if (vec) {  // uniform; N % 8 == 0: the piece lies inside the row
+                ra[i] = *reinterpret_cast<const uint4_t*>(grow[i] + na);
+            } else {
+                uint32_t h[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) h[j] = na + j < N ? (uint32_t)grow[i][na + j] : 0u;
+                ra[i] = uint4_t{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int n = nt * MX_DG_BN + bn4 * 4 + i;
+            rb[i] = (bk_ok && n < N) ? *reinterpret_cast<const uint32_t*>(wsrc + (long)n * KH) : 0u;
+        }
+        const int n = nt * MX_DG_BN + sn;
+        rs = (sb_ok && n < N) ? mx_rebias(ssrc[(long)n * KB], eb) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX_DG_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MX_DG_APITCH + c16 * 16) = ra[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {  // byte column 4 bd + i of rows 4 bn4 .. + 3
+            const uint32_t w = ((rb[0] >> (8 * i)) & 0xffu) | (((rb[1] >> (8 * i)) & 0xffu) << 8) | (((rb[2] >> (8 * i)) & 0xffu) << 16) |
+                               (((rb[3] >> (8 * i)) & 0xffu) << 24);
+            *reinterpret_cast<uint32_t*>(st + B_OFF + (bd * 4 + i) * MX_DG_BPITCH + bn4 * 4) = w;
+        }
+        reinterpret_cast<float*>(st + S_OFF)[sb * MX_DG_SPITCH + sn] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int nt = 0; nt < NT; nt++) {
+        const int buf = nt & 1;
+        if (nt + 1 < NT) load(nt + 1);
+        const unsigned char* st = lds + buf * MX_DG_STAGE;
+        const unsigned char* bcol = st + B_OFF + (wx * 32 + rl) * MX_DG_BPITCH + hh * 8;
+        const float* scol = reinterpret_cast<const float*>(st + S_OFF) + (wx * 2 + (rl >> 4)) * MX_DG_SPITCH + hh * 8;
+#pragma unroll
+        for (int ns = 0; ns < MX_DG_BN / 16; ns++) {
+            typename F::t a[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX_DG_APITCH + ns * 32 + hh * 16));
+            const uint2_t w = *reinterpret_cast<const uint2_t*>(bcol + ns * 16);
+            const float4_t s0 = *reinterpret_cast<const float4_t*>(scol + ns * 16), s1 = *reinterpret_cast<const float4_t*>(scol + ns * 16 + 4);
+            typename F::t b0, b1;  // output columns 2 rl and 2 rl + 1 of the wave's 64
+            mx_frag_columns<DT>(w.x, w.y, s0, s1, b0, b1);
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                acc[i][0] = F::mfma(a[i], b0, acc[i][0]);
+                acc[i][1] = F::mfma(a[i], b1, acc[i][1]);
+            }
+        }
+        if (nt + 1 < NT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: lane column rl = output columns k0 + wx 64 + 2 rl (acc[.][0]) and + 1 (acc[.][1]), tile row (r & 3) + 8 (r >> 2) + 4 hh
+    const int k = k0 + wx * 64 + 2 * rl;
+    if (k >= K) return;  // K % 32 == 0 and k is even: the pair lies inside K or outside
+    const float cs = e8m0_f32(eblk[k >> 5]);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (rows.live(row)) mx_store2<ODT>(gx, rows.dst(row) * K + k, acc[i][0][r] * cs, acc[i][1][r] * cs);
+        }
 }
 
 // ---- the routing workspace of the grouped expert GEMMs (mxm_route_kernel of mxfp4_moe.hip writes it; mxfp4_moe.hip and mxfp4_moe_a4.hip read it)

@@ -657,6 +657,29 @@ size_t bie_mxfp4_moe_workspace_bytes(long P, long E);
 int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                           void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 input gradient
+ * gx = gy . W straight from the packed weights of the mxfp4 and mxfp4 mixture-of-experts sections, for the backward of their layers
+ * ("MXFP4 input gradient").  qweight / scales are those sections', unchanged.
+ *   gx[m, k] = odt( sum_n gy[m, n] * W[n, k] ): products exact, the sum in fp32 in an order fixed by N alone, one rounding
+ *   e_blk    uint8 [K/32] ([E, K/32]): the largest scale code of block-column kb over the N rows (of expert e), 255 where one of its
+ *            blocks has scale code 255.  The kernels rebias by it: a block-column with e_blk == 255 is NaN in every row of gx; in fp16 a
+ *            block more than 2^14 below its block-column's largest scale loses bits and one more than 2^24 below it flushes to zero, in
+ *            bf16 the flush is at 2^126 below.
+ *   K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1 (gy rows need no alignment beyond 2 bytes); dtype fp16 or bf16.
+ * bie_mxfp4_blk_exp: scales [groups, rows, K/32] -> e_blk [groups, K/32]; groups = 1 for a linear layer, E (<= 1024) for experts.
+ * bie_mxfp4_linear_grad_input: gy [M, N] and gx [M, K] (16-byte aligned) in the dtype.
+ * bie_mxfp4_moe_grad_input: gy [P, N] (one row per pair, P = T * S), idx int32 [T, S], gx [P, K] in the dtype (out_fp32 = 0) or in fp32
+ *   (out_fp32 = 1); gx[p, :] = gy[p] . W[idx[p]], 0 where idx[p] is outside [0, E), and nothing is read through such an index.  A row of
+ *   gx depends on its own pair only.  workspace: bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned, need not be initialised.
+ *   1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22.
+ * One form each (a 128 x 128 tile GEMM on the matrix instructions): a small M is correct, not efficient.  Every argument is validated
+ * on the host before any device call; nothing synchronises with the host. */
+int bie_mxfp4_blk_exp(const uint8_t* scales, uint8_t* e_blk, long rows, long K, long groups, void* stream);
+int bie_mxfp4_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
+                                int dtype, void* stream);
+int bie_mxfp4_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
+                             void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp4 w4a4 mixture of experts
  * The expert GEMM of the section above with the activations quantised to MXFP4 on the fly, contracted on the block-scaled matrix
  * instructions (MXFP4A4ExpertsLinearCuda, MXFP4MoECuda(activations="mxfp4"); INTEGRATION.md, "MXFP4 W4A4 mixture-of-experts layer").
