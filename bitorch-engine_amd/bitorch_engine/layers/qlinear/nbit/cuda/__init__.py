@@ -9,3 +9,4 @@ from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda, MXFP4ExpertsLinearForwa
 from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda, MXFP4A4ExpertsLinearForward
 from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda, MXFP4A8ExpertsLinearForward
 from .mxfp4_moe_layer import MXFP4MoECuda
+from .mxfp6_a8_layer import MXFP6A8LinearCuda, MXFP6A8LinearForward

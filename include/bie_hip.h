@@ -753,6 +753,39 @@ int bie_mxfp4_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* r
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 w6a8
+ * MXFP6 (OCP microscaling FP6, E2M3 elements) weights x the MXFP8 activations of the mxfp4 w4a8 section (bie_mxfp8_quantize_act: xq, xs,
+ * row_flag, unchanged), contracted on the block-scaled matrix instructions with an FP6 and an E4M3 operand (MXFP6A8LinearCuda;
+ * INTEGRATION.md, "MXFP6 W6A8 linear layer").  No reference implementation; these definitions are this library's own.
+ *   qweight  uint8 [N, 3K/4] (16-byte aligned): per row K/32 blocks of 24 bytes in k order; code j of a block in bits 6 j .. 6 j + 5 of
+ *            the block's little-endian 192-bit integer.  Code: bit 5 sign, bits 4:3 exponent (bias 1), bits 2:0 mantissa; magnitudes
+ *            {0, 0.125 .. 0.875, 1 .. 1.875 step 0.125, 2 .. 3.75 step 0.25, 4 .. 7.5 step 0.5}; no Inf / NaN code
+ *   scales   uint8 [N, K/32]: E8M0 as in the mxfp4 section (255 = a NaN block); e_col = bie_mxfp4_col_exp(scales)
+ *   W[n, k]  = e2m3(code) * 2^(s - 127)   (exact in fp32)
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e4m3(xq[m,k]) * e2m3(qweight[n,k])) + bias[n] ): sums in fp32 in
+ *              any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ * bie_mxfp6_quantize: w [N, K] (dtype 0/1/2, 4-byte aligned) -> qweight / scales: per block of 32, in fp32, e = floor(log2 amax) - 2
+ *   clamped to [-127, 127], scale code e + 127, codes = |w / 2^e| clamped to 7.5 and rounded to the nearest E2M3 value (ties to the even
+ *   code), the sign bit follows w (-0.0 -> 0x20); an all-zero block gets scale code 0 and 24 zero bytes.  Idempotent on W.
+ * bie_mxfp6_dequant: -> W [N, K] in dtype 0/1/2 (computed in fp32, rounded once).
+ * bie_mxfp6_a8_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP6_A8_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mxfp6_a8_workspace_bytes: the bytes bie_mxfp6_a8_linear_forward needs: xq [M, K] (16-byte aligned), then xs, then row_flag, the
+ *   whole rounded up to 16 (any form); 0 for a shape the layer refuses.  Host only.  bie_mxfp6_a8_gemm needs no workspace (NULL is accepted).
+ * bie_mxfp6_a8_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction.  form -1 =
+ *   bie_mxfp6_a8_form.  e_col is required by both forms.
+ * bie_mxfp6_a8_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call, with the return codes of the w4a8 entries; nothing synchronises with
+ * the host. */
+int bie_mxfp6_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream);
+int bie_mxfp6_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long N, long K, int dtype, void* stream);
+int bie_mxfp6_a8_form(long M, long N, long K, int dtype);
+size_t bie_mxfp6_a8_workspace_bytes(long M, long N, long K, int form);
+int bie_mxfp6_a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                                void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                      const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,462 @@
+"""MXFP6 W6A8 linear layer on the MI355X: the weight quantiser and dequant bit-exact against the torch restatement (mxfp6_ref.py), the
+selector test that pins the k of every code of both operands, both forward forms against the float64 product of the restated x^ and W^
+within the tolerance of mxfp6_ref.py (its accumulation term from the probe's figure), exact data bit-identical across forms,
+forward == gemm(quantize_act), the test that tells the layer from the W4A8 one, the non-finite row rule, the scale-255 column rule,
+scale sums, the checkpoint rules, the straight-through backward, graph replay, 3-D / non-contiguous x and host-tensor refusal."""
+import importlib.util
+import os
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+DTS = [torch.float16, torch.bfloat16]
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+ref = _load("mxfp6_ref")
+ref48 = ref.a8  # mxfp4_a8_ref
+mx4 = ref.mx    # mxfp4_ref
+
+DECODE_ROWS = 64  # the decode form's largest M (bie_mxfp6_a8_linear_forward refuses it beyond)
+
+
+def ext():
+    from bitorch_engine.extensions import mxfp6_a8_linear_cuda
+    return mxfp6_a8_linear_cuda
+
+
+def forms(M):
+    return (0, 1) if M <= DECODE_ROWS else (1,)
+
+
+def rand_mx(N, K, g, lo=118, hi=130):
+    q = torch.randint(0, 256, (N, K // 32 * 24), generator=g, dtype=torch.int32).to(torch.uint8)
+    s = torch.randint(lo, hi + 1, (N, K // 32), generator=g, dtype=torch.int32).to(torch.uint8)
+    return q, s
+
+
+def check(y, yref, absprod, K, dt, what=""):
+    tol = ref.tolerance(yref, absprod, K, dt)
+    err = (y.double() - yref).abs()
+    print(f"{what} max err {err.max().item():.3e}, max err / tol {(err / tol).max().item():.3f}")
+    assert torch.isfinite(y).all()
+    assert (err <= tol).all(), f"{what} max err {err.max().item()} (tol there {tol.flatten()[err.argmax()].item()})"
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16, torch.float32])
+def test_weight_quantiser_is_bit_exact_and_dequant_exact(dt):
+    g = torch.Generator().manual_seed(1)
+    N, K = 37, 1024
+    lo, hi = (-22, 12) if dt == torch.float16 else (-130, 120)
+    e = torch.randint(lo, hi, (N, K // 32), generator=g).float().repeat_interleave(32, dim=1)
+    w = torch.randn((N, K), generator=g) * torch.exp2(e)
+    # ties and saturation at the block's own scale: amax 4 * 2^t (so the scaled values are the ones written here), values on E2M3
+    # midpoints in every range, both zeros; every value is a value of fp16 and of bf16
+    mids = torch.tensor([0.0625, 0.1875, 0.3125, 0.9375, 1.0625, 1.9375, 2.125, 2.375, 3.875, 0.0703125, 0.05859375, 1.5, 3.75, -0.0, 0.0, 0.03125])
+    for r in range(0, N, 3):
+        t = float(torch.randint(-8, 5, (1,), generator=g))
+        w[r, :32] = 0.0
+        w[r, 0] = 4.0 * 2.0 ** t
+        w[r, 1:1 + len(mids)] = mids * 2.0 ** t * torch.where(torch.rand(len(mids), generator=g) < 0.5, -1.0, 1.0)
+    # saturation: a block maximum in (7.5, 8) keeps e = t and clamps to 7.5 (7.75 is the midpoint to the absent 8; 7.9375 is the largest
+    # bf16 value below 8)
+    sat = ((1, 7.5625), (4, 7.75), (7, 7.875), (10, 7.9375))
+    for r, big in sat:
+        w[r, 32:64] = torch.randn(32, generator=g)
+        w[r, 32], w[r, 33], w[r, 34], w[r, 35] = big, -big, 4.25, -4.75
+    w[N - 1, 64:96] = 0.0    # an all-zero block
+    w[N - 2, 96:128] = -0.0  # a block of negative zeros
+    w = w.to(dt)
+    # subnormal amax (blocks of subnormals of the dtype) and amax at the dtype's largest value
+    if dt == torch.float32:
+        w[5] = (torch.arange(K, dtype=torch.int32) * 5 + 1).view(torch.float32)
+    else:
+        sub = torch.arange(32, dtype=torch.int16).repeat(K // 32)
+        w[5] = (sub + 1).view(dt) if dt == torch.float16 else (sub * 3 + 1).view(dt)
+    w[6, :32] = torch.finfo(dt).max * torch.linspace(-1, 1, 32).to(dt).float()
+    w[6, 32:64] = torch.finfo(dt).max * 0.49
+    w = w.to(dt)
+    assert torch.isfinite(w.float()).all()
+    c, s = ref.quantize(w)
+    assert (c[[1, 4, 7, 10], 32] == 31).all() and (c[[1, 4, 7, 10], 33] == 63).all()  # the restatement saturates there
+    assert (c[N - 2, 96:128] == 0).all() and s[N - 2, 3] == 0
+    want = ref.pack(c)
+    q, sg = ext().quantize(w.to(DEV))
+    assert q.shape == (N, 3 * K // 4) and torch.equal(sg.cpu(), s)
+    bad = (ref.unpack(q.cpu()) != c).nonzero()
+    assert bad.numel() == 0, [(int(r), int(k), float(w[r, k]), int(c[r, k]), int(ref.unpack(q.cpu())[r, k])) for r, k in bad[:8]]
+    assert torch.equal(q.cpu(), want)
+    for N2, K2 in ((3, 32), (5, 96), (300, 160)):  # one block, an odd block count, more than one workgroup
+        w2 = torch.randn((N2, K2), generator=g).to(dt)
+        c2, s2 = ref.quantize(w2)
+        q2, sg2 = ext().quantize(w2.to(DEV))
+        assert torch.equal(q2.cpu(), ref.pack(c2)) and torch.equal(sg2.cpu(), s2)
+    # the rule is idempotent on W^ (through the kernels), and dequant is exact: fp32 bit for bit, one rounding to the 16-bit dtypes
+    W = ext().dequant(q, sg, torch.float32)
+    assert torch.equal(W.cpu().double(), ref.dequant(want, s))
+    q3, s3 = ext().quantize(W)
+    assert torch.equal(q3, q) and torch.equal(s3, sg)
+    qr, sr = rand_mx(41, 160, g, 0, 254)  # every byte pattern, scale codes from 0 (2^-127) to 254
+    sr[0, 0], sr[3, 4] = 255, 255
+    Wr = ref.dequant(qr, sr)
+    for odt in (torch.float32, torch.float16, torch.bfloat16):
+        got = ext().dequant(qr.to(DEV), sr.to(DEV), odt).cpu()
+        exp = Wr.float().to(odt)  # W^ is exact in fp32
+        assert torch.equal(torch.isnan(got), torch.isnan(exp)) and torch.isnan(got[0, :32]).all() and torch.isnan(got[3, 128:160]).all()
+        bits = torch.int32 if odt == torch.float32 else torch.int16
+        bad = ((got.view(bits) != exp.view(bits)) & ~torch.isnan(exp)).nonzero()
+        assert bad.numel() == 0, (odt, [(int(ref.unpack(qr)[r, k]), int(sr[r, k // 32]), float(got[r, k]), float(exp[r, k])) for r, k in bad[:8]])
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("K", [128, 160])
+def test_selector_weights_pin_the_k_of_every_code_of_both_operands(K, dt):
+    """Weights one-hot: FP6 code 1.0 (0x08) at k = pi(n) under scale 2^0, all other codes 0; pi covers every k.  x holds distinct
+    E4M3-exact values per k under scale 2^0.  Then y[m, n] == x^[m, pi(n)] exactly, in both forms: a wrong bit position of a weight code
+    or a wrong k of an x byte selects another value."""
+    g = torch.Generator().manual_seed(K)
+    N = 2 * K + 3
+    pi = torch.cat([torch.randperm(K, generator=g), torch.randperm(K, generator=g), torch.tensor([0, K - 1, K // 2])])
+    codes = torch.zeros((N, K), dtype=torch.uint8)
+    codes[torch.arange(N), pi] = 0x08
+    q = ref.pack(codes)
+    s = torch.full((N, K // 32), 127, dtype=torch.uint8)
+    for M in (1, 17, 65):
+        # byte (m, k) = a code that differs along k within a row and between rows: 0x08 .. 0x77 (positive, 2^-6 .. 240, exact in fp16 / bf16)
+        xq = (0x08 + (torch.arange(K)[None, :] * 5 + torch.arange(M)[:, None] * 3) % 0x70).to(torch.uint8)
+        if K > 0x70:  # more k than codes: the second lap takes the negative codes
+            xq = torch.where(torch.arange(K)[None, :] >= 0x70, xq | 0x80, xq.to(torch.int32)).to(torch.uint8)
+        xs = torch.full((M, K // 32), 127, dtype=torch.uint8)
+        flag = torch.zeros(M, dtype=torch.uint8)
+        xh = ref.dequant_act(xq, xs)
+        assert all(len(set(row.tolist())) == K for row in xh)
+        want = xh[:, pi].to(dt)
+        assert torch.equal(want.double(), xh[:, pi])
+        for form in forms(M):
+            y = ext().gemm(xq.to(DEV), xs.to(DEV), flag.to(DEV), q.to(DEV), s.to(DEV), dtype=dt, form=form)
+            assert torch.equal(y.cpu(), want), (M, form, (y.cpu() != want).nonzero()[:5].tolist())
+    # and the other way round: x one-hot (1.0 at one k per row m), weights with a distinct nonzero code per k of a row
+    M = 64
+    wc = (torch.arange(K)[None, :] * 5 + torch.arange(N)[:, None] * 11) % 62 + 1
+    wc = torch.where(wc >= 32, wc + 1, wc).to(torch.uint8)  # 1 .. 31 and 33 .. 63: every nonzero value (32 is -0.0)
+    # the codes of one block are distinct (32 consecutive k); blocks are told apart by their scales 2^-12, 2^-6, .. (the magnitudes
+    # 0.125 .. 7.5 of one block lie below those of the next), and the values stay exact in fp16: no two k of a row give one value
+    sw = (127 + 6 * (torch.arange(K // 32) - 2))[None, :].repeat(N, 1).to(torch.uint8)
+    Wd = ref.dequant(ref.pack(wc), sw)
+    assert all(len(set(row.tolist())) == K for row in Wd[:8])
+    xq = torch.zeros((M, K), dtype=torch.uint8)
+    ks = (torch.arange(M) * 37 + 5) % K
+    xq[torch.arange(M), ks] = 0x38  # 1.0
+    xs = torch.full((M, K // 32), 127, dtype=torch.uint8)
+    flag = torch.zeros(M, dtype=torch.uint8)
+    want = Wd[:, ks].t().contiguous()
+    assert torch.equal(want.to(dt).double(), want)
+    for form in (0, 1):
+        y = ext().gemm(xq.to(DEV), xs.to(DEV), flag.to(DEV), ref.pack(wc).to(DEV), sw.to(DEV), dtype=dt, form=form)
+        assert torch.equal(y.cpu().double(), want), (form, (y.cpu().double() != want).nonzero()[:5].tolist())
+
+
+# every K of {32, 96, 160, 1024, 4096} (one block, an odd block count, a partial stage, waves with and without work) and every N of
+# {1, 3, 16, 17, 130, 257} (scalar and vector stores, a partial tile) at every M; the decode-range M also forced to the prefill form
+KN = ((32, 1), (96, 3), (160, 16), (1024, 17), (4096, 130), (160, 257), (32, 130), (96, 17), (1024, 3), (4096, 16))
+DECODE_M = (1, 5, 16, 17, 33, 64)
+PREFILL_M = (65, 130, 300)
+
+
+SHAPES = [(M, K, N) for M in DECODE_M + PREFILL_M for K, N in KN] + [(257, 160, 21846)]
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M,K,N", SHAPES)
+def test_forward_every_form_against_float64(M, K, N, dt):
+    """(257, 160, 21846): 3 x 171 = 513 tiles of 128 x 128, the (2, 2) tile instance with ragged edges in M, N and K."""
+    g = torch.Generator().manual_seed(M * 7 + K * 3 + N)
+    q, s = rand_mx(N, K, g)
+    x = (torch.randn((M, K), generator=g) * 0.5).to(dt)
+    bias = (torch.randn(N, generator=g)).to(dt) if (M + N) % 2 else None
+    xq, xs, flag = ref.quantize_act(x)
+    yref, a = ref.reference(xq, xs, flag, q, s, bias, DEV)
+    qd, sd = q.to(DEV), s.to(DEV)
+    e = ext().col_exp(sd)
+    for form in forms(M) + (-1,):
+        y = ext().forward(x.to(DEV), qd, sd, None if bias is None else bias.to(DEV), e, form=form)
+        assert y.dtype == dt and y.shape == (M, N)
+        check(y, yref, a, K, dt, f"form {form}")
+
+
+def exact_case(M, N, K, g, dt):
+    """x values k-dependent small integers x 2^j, j in -1 .. 1 (E4M3-exact, every block's amax the power of two 8 * 2^j, so x is a fixed
+    point of the quantiser); weight codes random, scales 126 .. 128.  |x| <= 8 * 2, |w| <= 7.5 * 2, granularity 2^-1 * 2^-3 * 2^-1: every
+    partial sum of K = 256 products is a multiple of 2^-5 below 256 * 16 * 15 < 2^16: 21 bits, exact in fp32."""
+    q, s = rand_mx(N, K, g, 126, 128)
+    j = torch.randint(-1, 2, (M, K // 32), generator=g).repeat_interleave(32, dim=1)
+    ints = ((torch.arange(K)[None, :] * 3 + torch.arange(M)[:, None]) % 15 - 7).float()
+    ints[:, ::32] = 8.0  # the block maximum
+    x = (ints * torch.exp2(j.float())).to(dt)
+    return x, q, s
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M", [1, 5, 16, 33, 64, 300])
+def test_exact_data_is_bit_identical_across_forms_and_against_float64(M, dt):
+    g = torch.Generator().manual_seed(M)
+    N, K = 72, 256
+    x, q, s = exact_case(M, N, K, g, dt)
+    xq, xs, flag = ref.quantize_act(x)
+    assert torch.equal(ref.dequant_act(xq, xs), x.double())  # x is a fixed point: x^ == x
+    bias = torch.randint(-8, 9, (N,), generator=g).to(dt)
+    yref, _ = ref.reference(xq, xs, flag, q, s, bias, DEV)
+    assert torch.equal(yref.float().double(), yref)
+    want = yref.to(dt)
+    for form in forms(M) + (-1,):
+        y = ext().gemm(xq.to(DEV), xs.to(DEV), flag.to(DEV), q.to(DEV), s.to(DEV), bias.to(DEV), dtype=dt, form=form)
+        assert torch.equal(y, want), (form, (y.double() - want.double()).abs().max().item())
+        y = ext().forward(x.to(DEV), q.to(DEV), s.to(DEV), bias.to(DEV), form=form)
+        assert torch.equal(y, want), ("forward", form)
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M", [3, 40, 64, 130])
+def test_forward_is_gemm_of_quantize_act(M, dt):
+    g = torch.Generator().manual_seed(M + 11)
+    N, K = 77, 416
+    q, s = rand_mx(N, K, g)
+    x = torch.randn((M, K), generator=g).to(dt).to(DEV)
+    bias = torch.randn(N, generator=g).to(dt).to(DEV)
+    xq, xs, flag = ext().quantize_act(x)
+    for form in forms(M):
+        assert torch.equal(ext().forward(x, q.to(DEV), s.to(DEV), bias, form=form),
+                           ext().gemm(xq, xs, flag, q.to(DEV), s.to(DEV), bias, dtype=dt, form=form)), form
+
+
+def layer_with(cls, N, K, dt, bias=False, seed=0):
+    torch.manual_seed(seed)
+    return cls(K, N, bias=bias, dtype=dt).to(DEV)
+
+
+def layers():
+    from bitorch_engine.layers.qlinear.nbit.cuda import MXFP4A8LinearCuda, MXFP4LinearCuda, MXFP6A8LinearCuda
+    return MXFP6A8LinearCuda, MXFP4A8LinearCuda, MXFP4LinearCuda
+
+
+# The share of outputs where the W4A8 restatement of the same latent weight lies outside the W6A8 tolerance, from the two restatements
+# alone on the CPU (both dtypes, the shapes below): 87.5 % or more (least at bf16 (8, 4096, 256)).  Less than half of the smallest share
+# is asked.
+OUTSIDE_W4 = 0.43
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M,K,N", [(8, 4096, 256), (64, 1024, 128), (3, 32, 16), (200, 1024, 128)])
+def test_the_layer_is_w6a8_and_not_w4a8(M, K, N, dt):
+    W6, W4A8, _ = layers()
+    g = torch.Generator().manual_seed(K + M)
+    w = torch.randn((N, K), generator=g).to(dt)
+    x = torch.randn((M, K), generator=g).to(dt)
+    l6, l4 = layer_with(W6, N, K, dt).eval(), layer_with(W4A8, N, K, dt).eval()
+    with torch.no_grad():
+        l6.weight.copy_(w)
+        l4.weight.copy_(w)
+        y6, y4 = l6(x.to(DEV)), l4(x.to(DEV))
+    assert not torch.equal(y6, y4)
+    xq, xs, flag = ref.quantize_act(x)
+    c6, s6 = ref.quantize(w)
+    c4, s4 = mx4.quantize(w)
+    assert torch.equal(l6.qweight.cpu(), ref.pack(c6)) and torch.equal(l6.scales.cpu(), s6)
+    r6, a6 = ref.reference(xq, xs, flag, ref.pack(c6), s6, None, DEV)
+    r4, a4 = ref48.reference(xq, xs, flag, mx4.pack(c4), s4, None, DEV)
+    check(y6, r6, a6, K, dt, "w6a8 layer against the w6a8 restatement")
+    tol4 = ref48.tolerance(r4, a4, K, dt)
+    out_ref = ((r6 - r4).abs() > tol4).double().mean().item()
+    out = ((y6.double() - r4).abs() > tol4).double().mean().item()
+    print(f"outside the W4A8 tolerance of the W4A8 restatement: the W6A8 restatement {100 * out_ref:.1f} %, the layer {100 * out:.1f} %")
+    assert out_ref > OUTSIDE_W4 and out > OUTSIDE_W4
+    check(y4, r4, a4, K, dt, "w4a8 layer against the w4a8 restatement")  # the yardstick does tell the two apart: each layer passes its own
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_scale_sums_between_minus_100_and_100(dt):
+    """Chosen scales at the ends of the tested range: sx + sw - 254 in [-100, 100], one block of small integers so the fp32 value is exact."""
+    g = torch.Generator().manual_seed(4)
+    N, K, M = 48, 32, 40
+    q, _ = rand_mx(N, K, g)
+    xq = torch.randint(-15, 16, (M, K), generator=g).float().to(torch.float8_e4m3fn).view(torch.uint8)
+    for sx, sw in ((27, 127), (127, 27), (77, 77), (227, 127), (127, 227), (177, 177), (2, 252), (252, 2)):
+        xs = torch.full((M, 1), sx, dtype=torch.uint8)
+        s = torch.full((N, 1), sw, dtype=torch.uint8)
+        flag = torch.zeros(M, dtype=torch.uint8)
+        yref, a = ref.reference(xq, xs, flag, q, s, None, DEV)
+        want = yref.float()  # exact: one block sum (32 products of 4 x 5 bits, multiples of 2^-3 below 2^12) times a power of two
+        assert torch.equal(want.double(), yref)
+        for form in forms(M):
+            # through the fp32 value: the dtype's rounding of the exact result (fp16 saturates to inf / flushes, as torch's cast does)
+            y = ext().gemm(xq.to(DEV), xs.to(DEV), flag.to(DEV), q.to(DEV), s.to(DEV), dtype=dt, form=form)
+            assert torch.equal(y, want.to(dt)), (sx, sw, form)
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M", [3, 64, 70])
+def test_non_finite_row_gives_a_nan_row_and_leaves_the_others_alone(M, dt):
+    g = torch.Generator().manual_seed(6)
+    N, K = 45, 256
+    q, s = rand_mx(N, K, g)
+    x = torch.randn((M, K), generator=g).to(dt)
+    clean = {form: ext().forward(x.to(DEV), q.to(DEV), s.to(DEV), form=form) for form in forms(M)}
+    for bad, pos in ((float("inf"), 0), (float("-inf"), K - 1), (float("nan"), 5), (float("nan"), K - 32)):
+        for row in (0, M - 1, M // 2):
+            xb = x.clone()
+            xb[row, pos] = bad
+            for form in forms(M):
+                y = ext().forward(xb.to(DEV), q.to(DEV), s.to(DEV), form=form)
+                assert torch.isnan(y[row]).all(), (bad, pos, row, form)
+                keep = torch.ones(M, dtype=torch.bool)
+                keep[row] = False
+                assert torch.equal(y[keep], clean[form][keep]), (bad, pos, row, form)
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_scale_255_gives_nan_in_that_column_only(dt):
+    g = torch.Generator().manual_seed(5)
+    N, K = 40, 256
+    q, s = rand_mx(N, K, g)
+    x = torch.randn((70, K), generator=g).to(dt)
+    bias = torch.randn(N, generator=g).to(dt)
+    s_bad = s.clone()
+    s_bad[3, 2] = 255
+    s_bad[39, 7] = 255
+    keep = torch.ones(N, dtype=torch.bool, device=DEV)
+    keep[3] = keep[39] = False
+    for M in (1, 16, 64, 70):
+        xq, xs, flag = ref.quantize_act(x[:M])
+        yref, a = ref.reference(xq, xs, flag, q, s_bad, bias, DEV)
+        for form in forms(M):
+            clean = ext().forward(x[:M].to(DEV), q.to(DEV), s.to(DEV), bias.to(DEV), form=form)
+            y = ext().forward(x[:M].to(DEV), q.to(DEV), s_bad.to(DEV), bias.to(DEV), form=form)
+            assert torch.isnan(y[:, 3]).all() and torch.isnan(y[:, 39]).all()
+            assert torch.equal(y[:, keep], clean[:, keep])  # the other columns are bit-identical to the run without the NaN blocks
+            check(y[:, keep], yref[:, keep], a[:, keep], K, dt, f"M {M} form {form}")
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_state_dict_round_trip_and_mxfp4_refusal(dt):
+    W6, W4A8, W4 = layers()
+    g = torch.Generator().manual_seed(3)
+    N, K = 48, 192
+    q, s = rand_mx(N, K, g)
+    x = torch.randn((5, K), generator=g).to(dt).to(DEV)
+    a = layer_with(W6, N, K, dt, bias=True).eval()
+    a.set_mx_weight(q.reshape(N, K // 32, 24), s)
+    assert set(a.state_dict()) == {"qweight", "scales", "bias"} and a.weight is None
+    assert torch.equal(a(x), ext().forward(x, q.to(DEV), s.to(DEV), a.bias.detach()))
+    b = layer_with(W6, N, K, dt, bias=True, seed=5).eval()
+    b.load_state_dict(a.state_dict())  # a packed checkpoint drops the latent weight
+    assert b.weight is None and torch.equal(b.qweight, a.qweight) and torch.equal(b(x), a(x))
+    lat = layer_with(W6, N, K, dt, bias=True, seed=7).eval()
+    y_lat = lat(x)
+    assert set(lat.state_dict()) == {"weight", "qweight", "scales", "bias"}
+    fresh = layer_with(W6, N, K, dt, bias=True, seed=8).eval()
+    fresh.load_state_dict(lat.state_dict())  # a latent-weight checkpoint: qweight is re-derived from the weight
+    assert torch.equal(fresh(x), y_lat) and torch.equal(fresh.qweight, lat.qweight) and torch.equal(fresh.scales, lat.scales)
+    b.load_state_dict(lat.state_dict())  # ... also into a layer that had dropped its own
+    assert b.weight is not None and torch.equal(b(x), y_lat)
+    fresh.generate_quantized_weight(qweight_only=True)
+    assert "weight" not in fresh.state_dict() and torch.equal(fresh(x), y_lat)
+    for cls in (W4, W4A8):
+        other = layer_with(cls, N, K, dt, bias=True).eval()
+        other(x)
+        before = fresh.qweight.clone()
+        with pytest.raises(RuntimeError, match="MXFP4 weight"):
+            fresh.load_state_dict(other.state_dict())
+        assert torch.equal(fresh.qweight, before) and torch.equal(fresh(x), y_lat)
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_backward_and_one_optimiser_step(dt):
+    W6, _, _ = layers()
+    N, K, M = 64, 128, 24
+    layer = layer_with(W6, N, K, dt, bias=True).train()
+    x = torch.randn((M, K), device=DEV).to(dt).requires_grad_(True)
+    y = layer(x)
+    q, s = ext().quantize(layer.weight.detach())
+    assert torch.equal(y.detach(), ext().forward(x.detach(), q, s, layer.bias.detach()))
+    gy = torch.randn_like(y)
+    y.backward(gy)
+    W = ref.dequant(q.cpu(), s.cpu()).to(DEV)
+    xq, xs, _ = ref.quantize_act(x.detach().cpu())
+    xh = ref.dequant_act(xq, xs).to(DEV)
+    # the float64 formulas; the layer computes them in fp32 and rounds once to the dtype
+    eps = 2.0 ** -10 if dt == torch.float16 else 2.0 ** -7
+    for got, want, absw in ((x.grad, gy.double() @ W, gy.double().abs() @ W.abs()),
+                            (layer.weight.grad, gy.double().t() @ xh, gy.double().abs().t() @ xh.abs()),
+                            (layer.bias.grad, gy.double().sum(0), gy.double().abs().sum(0))):
+        tol = eps * want.abs() + (M + N + 2) * 2.0 ** -23 * absw + 2.0 ** -24
+        assert ((got.double() - want).abs() <= tol).all()
+    # the weight gradient uses the QUANTISED activations: it differs from gy^T . x
+    assert not torch.equal(layer.weight.grad, gy.float().t().mm(x.detach().float()).to(dt))
+    before = layer(x).detach()
+    torch.optim.SGD(layer.parameters(), lr=0.5).step()
+    assert not torch.equal(layer(x).detach(), before)
+    # eval with grad enabled is differentiable in x
+    layer.eval()
+    x2 = torch.randn((M, K), device=DEV).to(dt).requires_grad_(True)
+    layer(x2).sum().backward()
+    assert x2.grad is not None and torch.isfinite(x2.grad).all()
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("M", [1, 8, 64, 200])
+def test_graph_replay_equals_eager(M, dt):
+    W6, _, _ = layers()
+    N, K = 256, 512
+    layer = layer_with(W6, N, K, dt, bias=True).eval()
+    x = torch.randn((M, K), device=DEV).to(dt)
+    with torch.no_grad():
+        eager = layer(x)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            layer(x)
+        torch.cuda.current_stream().wait_stream(s)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            out = layer(x)
+        x.copy_(torch.randn((M, K), device=DEV).to(dt))
+        gr.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, layer(x))
+        assert not torch.equal(out, eager)
+
+
+@pytest.mark.parametrize("dt", DTS)
+def test_3d_and_non_contiguous_x(dt):
+    W6, _, _ = layers()
+    N, K = 40, 256
+    layer = layer_with(W6, N, K, dt).eval()
+    base = torch.randn((K, 6), device=DEV).to(dt)
+    x = base.t()
+    assert not x.is_contiguous()
+    with torch.no_grad():
+        assert torch.equal(layer(x), layer(x.contiguous()))
+        x3 = torch.randn((2, 3, K), device=DEV).to(dt)
+        y3 = layer(x3)
+        assert y3.shape == (2, 3, N) and torch.equal(y3.reshape(6, N), layer(x3.reshape(6, K)))
+
+
+def test_host_tensor_is_refused():
+    W6, _, _ = layers()
+    layer = layer_with(W6, 8, 64, torch.float16).eval()
+    with pytest.raises(RuntimeError):
+        layer(torch.randn((2, 64)).half())
+    with pytest.raises(RuntimeError):
+        ext().quantize(torch.randn((2, 64)))
+    with pytest.raises(RuntimeError):
+        ext().forward(torch.zeros((65, 64), dtype=torch.half, device=DEV), layer.qweight, layer.scales, form=0)  # no fallback past M = 64
