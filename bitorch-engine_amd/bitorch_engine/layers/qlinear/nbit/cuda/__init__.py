@@ -10,3 +10,5 @@ from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda, MXFP4A4ExpertsLine
 from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda, MXFP4A8ExpertsLinearForward
 from .mxfp4_moe_layer import MXFP4MoECuda
 from .mxfp6_a8_layer import MXFP6A8LinearCuda, MXFP6A8LinearForward
+from .mxfp6_experts_a8_layer import MXFP6A8ExpertsLinearCuda, MXFP6A8ExpertsLinearForward
+from .mxfp6_moe_layer import MXFP6MoECuda

@@ -21,6 +21,40 @@ from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda
 mxfp4_experts_a8_cuda = import_extension("mxfp4_experts_a8_cuda")
 
 
+def experts_a8_backward(ext, K, ctx, gy):
+    """The straight-through backward of an expert layer with MXFP8 activations; ext supplies dequant (the weight format's) and
+    quantize_act / dequant_act, K is the layer's input width.  Shared by the MXFP4 and the MXFP6 expert layers."""
+    x, idx, qweight, scales = ctx.saved_tensors
+    E, N = qweight.shape[0], qweight.shape[1]
+    T, S = idx.shape
+    need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+    g = gy.reshape(T * S, N).float()
+    flat = idx.reshape(-1).long()
+    gx = torch.zeros((T * S, K), dtype=torch.float32, device=gy.device) if need_x else None
+    gw = torch.zeros((E, N, K), dtype=torch.float32, device=gy.device) if need_w else None
+    gb = torch.zeros((E, N), dtype=torch.float32, device=gy.device) if need_b else None
+    W = ext.dequant(qweight, scales, torch.float32) if need_x else None
+    xr = None
+    if need_w:  # x^ of the stored rows, then a row per pair
+        xq, xs, _ = ext.quantize_act(x.reshape(-1, K))
+        xh = ext.dequant_act(xq, xs, torch.float32)
+        xr = (xh.reshape(T, S, K) if x.dim() == 3 else xh[:, None, :].expand(T, S, K)).reshape(T * S, K)
+    for e in range(E):
+        rows = (flat == e).nonzero().reshape(-1)
+        if rows.numel() == 0:
+            continue
+        ge = g[rows]
+        if need_x:
+            gx[rows] = ge.mm(W[e])
+        if need_w:
+            gw[e] = ge.t().mm(xr[rows])
+        if need_b:
+            gb[e] = ge.sum(0)
+    if need_x:
+        gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
+    return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
+
+
 class MXFP4A8ExpertsLinearForward(Function):
     """Forward: the W4A8 expert kernels.  Backward (straight-through estimator, in fp32, cast to the dtype), over the live pairs p of expert e:
       grad_x[row(p)] += gy[p] . W[e]        (identity through the activation quantiser; summed over a token's slots when x is [T, K])
@@ -36,35 +70,7 @@ class MXFP4A8ExpertsLinearForward(Function):
     @staticmethod
     @typing.no_type_check
     def backward(ctx, gy):
-        x, idx, qweight, scales = ctx.saved_tensors
-        E, N, K = qweight.shape[0], qweight.shape[1], qweight.shape[2] * 2
-        T, S = idx.shape
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        g = gy.reshape(T * S, N).float()
-        flat = idx.reshape(-1).long()
-        gx = torch.zeros((T * S, K), dtype=torch.float32, device=gy.device) if need_x else None
-        gw = torch.zeros((E, N, K), dtype=torch.float32, device=gy.device) if need_w else None
-        gb = torch.zeros((E, N), dtype=torch.float32, device=gy.device) if need_b else None
-        W = mxfp4_experts_a8_cuda.dequant(qweight, scales, torch.float32) if need_x else None
-        xr = None
-        if need_w:  # x^ of the stored rows, then a row per pair
-            xq, xs, _ = mxfp4_experts_a8_cuda.quantize_act(x.reshape(-1, K))
-            xh = mxfp4_experts_a8_cuda.dequant_act(xq, xs, torch.float32)
-            xr = (xh.reshape(T, S, K) if x.dim() == 3 else xh[:, None, :].expand(T, S, K)).reshape(T * S, K)
-        for e in range(E):
-            rows = (flat == e).nonzero().reshape(-1)
-            if rows.numel() == 0:
-                continue
-            ge = g[rows]
-            if need_x:
-                gx[rows] = ge.mm(W[e])
-            if need_w:
-                gw[e] = ge.t().mm(xr[rows])
-            if need_b:
-                gb[e] = ge.sum(0)
-        if need_x:
-            gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
-        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
+        return experts_a8_backward(mxfp4_experts_a8_cuda, ctx.saved_tensors[2].shape[2] * 2, ctx, gy)
 
 
 class MXFP4A8ExpertsLinearCuda(MXFP4ExpertsLinearCuda):

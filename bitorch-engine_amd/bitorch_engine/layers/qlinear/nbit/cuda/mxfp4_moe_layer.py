@@ -57,10 +57,14 @@ class MXFP4MoECuda(nn.Module):
         self.swiglu_limit, self.swiglu_alpha, self.dtype = float(swiglu_limit), float(swiglu_alpha), dtype
         self.router = nn.Linear(hidden, num_experts, bias=bias, device=device, dtype=dtype)
         self.activations = activations
-        experts = _EXPERTS[activations]
+        experts = self._experts_class(activations)
         self.gate_up = experts(num_experts, hidden, 2 * intermediate, bias=bias, device=device, dtype=dtype)
         self.down = experts(num_experts, intermediate, hidden, bias=bias, device=device, dtype=dtype)
         self.register_buffer("expert_mask", None, persistent=False)
+
+    def _experts_class(self, activations: str):
+        """The class of gate_up and down (a subclass with another weight format returns its own)."""
+        return _EXPERTS[activations]
 
     def set_expert_mask(self, mask: torch.Tensor = None) -> None:
         """bool [E]: True for the experts this instance computes (None: all of them)."""
@@ -73,12 +77,15 @@ class MXFP4MoECuda(nn.Module):
     def load_gpt_oss_experts(self, gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias) -> None:
         """The checkpoint's expert tensors as they are: *_blocks uint8 [E, N, K/32, 16], *_scales uint8 [E, N, K/32], *_bias [E, N]
         (None for a block without bias)."""
+        self._load_experts("load_gpt_oss_experts", gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias)
+
+    def _load_experts(self, what, gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias) -> None:
         self.gate_up.set_mx_weight(gate_up_blocks, gate_up_scales)
         self.down.set_mx_weight(down_blocks, down_scales)
         with torch.no_grad():
             for layer, b in ((self.gate_up, gate_up_bias), (self.down, down_bias)):
                 if (b is None) != (layer.bias is None):
-                    raise ValueError("load_gpt_oss_experts: a bias is given for a block built without one (or the reverse)")
+                    raise ValueError(f"{what}: a bias is given for a block built without one (or the reverse)")
                 if b is not None:
                     layer.bias.copy_(b.reshape(layer.bias.shape))
 

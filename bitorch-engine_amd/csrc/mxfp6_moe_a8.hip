@@ -1,0 +1,295 @@
+// MXFP6 W6A8 expert GEMM for gfx950: stacked MXFP6 expert weights (E2M3 elements, E8M0 block scales; the format of mxfp6_a8.hip per
+// expert) against activations quantised to MXFP8 (E4M3 elements, E8M0 block scales) on the fly, contracted on the block-scaled matrix
+// instructions with an FP6 A operand and an E4M3 B operand (include/bie_hip.h, INTEGRATION.md "MXFP6 W6A8 mixture-of-experts layer").
+// It is mxfp4_moe_a8.hip with the weight side of mxfp6_a8.hip.  No reference implementation exists.
+//
+//   T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p]; row(p) = p / S (x_per_pair = 0) or p
+//   qweight uint8 [E, N, 3K/4]: per row K/32 blocks of 24 bytes, code j of a block in bits 6 j .. 6 j + 5 (the dense layer's bit order)
+//   scales uint8 [E, N, K/32]; e_col uint8 [E, N] = bie_mxfp4_col_exp on the [E * N, K/32] view
+//   xq uint8 [R, K] (e4m3fn bytes) / xs uint8 [R, K/32] / row_flag uint8 [R]: the stored rows of x (R = T or P) by the rule of
+//   mxa8_quantize_kernel (mxfp4_a8.hip)
+//   y[p, n] = dt( sum_b 2^(xs[row(p), b] + scales[e, n, b] - 254) * (sum_{k in b} e4m3(xq) * e2m3(qweight)) + bias[e, n] ),  e = idx[p]
+//   y[p, :] = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255; y[p, :] = +0 where idx[p] is outside [0, E), whatever
+//   the row's flag: the index is compared before any address is formed from it
+//
+// A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
+// row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
+//
+// Routed decode form (mx6m_decode_kernel, P <= 1024): a workgroup per pair and strip of 16 C16 columns of its expert, K split over the
+// 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4 in the operand order of mxfp6_a8.hip (profiles/mxfp6_a8_probe.txt):
+// the weight fragment is A (FP6, cbsz 2; three non-temporal 8-byte pieces at row * KB * 24 + block * 24, a6_frag: a block is only
+// 8-byte aligned), the x fragment B (E4M3, blgp 0, the two halves of a8_frag), byte select 0.  The pair's row is column 0 of B, so the
+// lanes with (lane & 15) == 0 carry it; all other columns are zero codes under scale code 127.  The four partial sums meet in LDS and
+// are summed as ((w0 + w1) + w2) + w3, the order of mx6a8_decode_kernel: a pair's row has the bits of the dense W6A8 decode form.
+// FUSED (one launch, K <= MX6M_ONE_K): the workgroup quantises x_row(p) into LDS itself (a8_quantize_unit, the bits of
+// mxa8_quantize_kernel; codes, scale bytes, and the non-finite flag through the barrier) and reads neither xq nor a workspace.  Not
+// FUSED: it reads xq / xs / row_flag from memory.
+// Grouped prefill form: mxa8_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
+// mx6m_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx6a8_gemm_tile (mxfp6_common.cuh) at 128 x 64.  A row tile belongs to one
+// expert, gathers the xq / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the segment enter
+// as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no
+// K loop and store zeros.
+#include "mxfp6_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// mxfp4_a8.hip, mxfp4_moe.hip
+int mxfp4_a8_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
+size_t mxfp4_moe_workspace_bytes(long P, long E);
+long mxfp4_moe_max_tiles(long P, long E);
+int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
+
+// ---- routed decode form -------------------------------------------------------------------------------------------------------------------
+// The largest K of the one-launch form: a row's image in LDS is the W4A8 expert kernel's (K bytes of codes and K / 32 scale bytes, 16896
+// bytes at the bound), so its bound carries over.
+constexpr int MX6M_ONE_K = 16384;
+constexpr int MX6M_DECODE_PAIRS = 1024;  // the grid's second dimension
+
+// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
+// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step's weights; the lanes
+// with (l & 15) == 0 hold the x bytes 16 (l >> 4) .. + 15 and 64 + 16 (l >> 4) .. + 15 of the step and the x scale of block l >> 4.
+// xin is x (FUSED) or xq.
+template <int DT, int C16, bool FUSED>
+__global__ __launch_bounds__(256) void mx6m_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                          const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                          const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                          int N, int K, int x_per_pair) {
+    constexpr int C = 16 * C16;
+    __shared__ float red[4][C];
+    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MX6M_ONE_K + MX6M_ONE_K / 32 : 16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int p = blockIdx.y, n0 = blockIdx.x * C;
+    const int e = idx[p];
+    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
+        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
+        return;
+    }
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const long xrow = x_per_pair ? p : p / S;
+    const uint8_t* xqr = nullptr;
+    const uint8_t* xsr = nullptr;
+    int flagged;
+    if constexpr (FUSED) {
+        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
+        const int U = K >> 3;  // a multiple of 4: whole quads are in or out
+        int bad = 0;
+        for (int u = t; u < U; u += 256) {
+            uint2_t codes;
+            uint32_t scode;
+            a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
+            reinterpret_cast<uint2_t*>(img)[u] = codes;
+            if ((u & 3) == 0) img[K + (u >> 2)] = (unsigned char)scode;
+        }
+        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
+    } else {
+        xqr = reinterpret_cast<const uint8_t*>(xin) + xrow * K;
+        xsr = xs + xrow * KB;
+        flagged = row_flag[xrow];
+    }
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+    const uint8_t* wrow[C16];
+    const uint8_t* srow[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) {
+        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
+        wrow[c] = qw + n * ((long)KB * MX6_BLOCK_BYTES);
+        srow[c] = sc + n * KB;
+    }
+    mxa4_v4f acc[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint2_t w0[C16], w1[C16], w2[C16];
+        int sw[C16];
+#pragma unroll
+        for (int c = 0; c < C16; c++) {
+            const uint2_t* wp = reinterpret_cast<const uint2_t*>(wrow[c] + (long)kc * MX6_BLOCK_BYTES);
+            w0[c] = __builtin_nontemporal_load(wp);
+            w1[c] = __builtin_nontemporal_load(wp + 1);
+            w2[c] = __builtin_nontemporal_load(wp + 2);
+            sw[c] = __builtin_nontemporal_load(srow[c] + kc);
+        }
+        // this lane's x halves: 16 bytes of block kq >> 1 of the step and 16 bytes of that block + 2, at offset 16 (kq & 1) in each
+        const int kb0 = s * 4 + (kq >> 1), kb1 = kb0 + 2;
+        uint4_t a0 = uint4_t{0u, 0u, 0u, 0u}, a1 = uint4_t{0u, 0u, 0u, 0u};
+        int sa = 127;
+        if (r16 == 0) {
+            const int o0 = kb0 * 32 + (kq & 1) * 16, o1 = kb1 * 32 + (kq & 1) * 16;
+            if constexpr (FUSED) {
+                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(img + o0);
+                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(img + o1);
+                if (kin) sa = img[K + kb];
+            } else {
+                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(xqr + o0);
+                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(xqr + o1);
+                if (kin) sa = xsr[kb];
+            }
+        }
+        if (!kin) {
+#pragma unroll
+            for (int c = 0; c < C16; c++) {
+                w0[c] = w1[c] = w2[c] = uint2_t{0u, 0u};
+                sw[c] = 127;
+            }
+        }
+        const mxa4_v8i fx = a8_frag(a0, a1);
+#pragma unroll
+        for (int c = 0; c < C16; c++)
+            acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a6_frag(w0[c], w1[c], w2[c]), fx, acc[c], 2, 0, 0, sw[c], 0, sa);
+    }
+    // C/D: D column (= row of the x operand) = lane & 15, D row (= column n of the strip) = 4 (lane >> 4) + r: the pair's row is
+    // registers 0 .. 3 of lanes 0, 16, 32, 48
+    if (r16 == 0) {
+#pragma unroll
+        for (int c = 0; c < C16; c++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) red[wave][c * 16 + 4 * kq + r] = acc[c][r];
+    }
+    __syncthreads();
+    if (t < C) {
+        const int n = n0 + t;
+        if (n < N) {
+            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
+            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
+            dt_traits<DT>::store(y, (long)p * N + n, v);
+        }
+    }
+}
+
+// ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
+// 128 x 64: the routing's row tile fixes WM = 2; with WN = 1 the tile's two buffers and the pair list take 52224 bytes of LDS.  (The
+// 128 x 128 instance's buffers alone are the 65536 bytes of static LDS; beside prow[] it would need 66048, which nothing in this
+// library has launched.)
+constexpr int MX6M_WM = 2, MX6M_WN = 1;
+static_assert(64 * MX6M_WM == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
+
+// A workgroup per (row tile of the table, column tile): mx6a8_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+template <int DT>
+__global__ __launch_bounds__(256) void mx6m_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                        const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                        const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                        int N, int K, int x_per_pair, int max_tiles) {
+    __shared__ int prow[MXM_BM];
+    int e, n0;
+    if (!mxm_tile_begin<DT, 64 * MX6M_WN>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
+    mx6a8_gemm_tile<DT, MX6M_WM, MX6M_WN>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The routed decode form exists for P <= MX6M_DECODE_PAIRS.  The plan started from the W4A8 expert layer's constants (decode for P <= 32,
+// and up to 128 while P <= E) and was then measured (tools/mxfp6_moe_a8_bench.py, profiles/mxfp6_moe_a8_bench.jsonl, the `sweep` rows:
+// both gpt-oss-20b projections at E = 32 and E = 128, fp16 and bf16, both forms forced at P = 1, 2, 4, ..., 1024, graph time, routings
+// and weight stacks rotated; fp16 and bf16 agree within 2 % but for 12 of the 88 figures, all at P <= 8, up to 9 %: no verdict below turns on that).  The decode form streams an expert's
+// weights once per pair, 1.5 x the W4A8 form's bytes, and grows linearly in P (9.8 / 23.3 / 81 / 157 / 311 / 619 us at
+// P = 1 / 4 / 16 / 32 / 64 / 128 on 2880 -> 5760; the W4A8 form took 7.5 / 15.2 / 47 / 90 / 175 / 349); the grouped form costs 37 us at
+// P = 1 (three launches, one row tile walking K) and then grows with the number of experts that hold a pair, on the narrower 128 x 64
+// tile.  At E = 32 the decode form led at every P <= 16 (at most 0.75 x the grouped form's time); P = 32 was level on 2880 -> 5760
+// (157.5 against 157.2 us in fp16, 157.9 against 158.3 in bf16) and ahead on 2880 -> 2880 (81 against 103 - 105); the grouped form led
+// from P = 64 on (311 against 207, 158 against 109).  At E = 128, where nearly every pair of a small call has an expert of its own, the
+// decode form led through P = 64 (308 against 341 - 348, 160 against 196 - 201) and the grouped form from P = 128 on (610 against
+// 498 - 506, 315 - 317 against 282 - 295; 1.08 - 1.22 x).  So the plan takes the decode form for P <= 32, and up to P = 64 while
+// 2 P <= E.  The second bound is narrower than the W4A8 layer's (128 while P <= E): the extra weight bytes are paid once per pair in
+// the decode form and once per (expert, row tile) in the grouped one, so the crossover moved down; the W4A8 constants would lose
+// 8 - 22 % at E = 128, P = 128.  E between 32 and 128 and beyond 128, and P between the powers of two, were not measured: the second
+// clause extends the E = 128 rows by the pairs-per-expert argument (P = 64 at E = 128 is half a pair per expert; P = 32 at E = 32, one
+// pair per expert, was level).  (The rows' `plan` column is the plan of the build that measured them, the W4A8 constants 32 / 128 /
+// P <= E, which these rows replaced; the `accept` rows ran P = 4, 64, 1024 and 16384 at E = 32, where both plans choose alike.)
+// The `accept` rows compare with the W4A8 expert layer on the same shapes, routings and activations (E = 32, S = 4, each arm one
+// graph, alternated for 9 rounds, the W4A8 arm's spread 0.1 - 0.5 % but for one row at 6 %): T = 1 (decode) 1.52 - 1.56 x its time,
+// above the 1.47 x of the weight bytes, as the dense W6A8 layer is at M = 1 (three 8-byte loads per lane and step); the grouped form
+// 1.06 - 1.08 x on 2880 -> 2880 and 1.23 - 1.27 x on 2880 -> 5760 at T = 16 / 256, and 1.32 - 1.34 x at T = 4096 (450 / 377 against
+// 602 / 499 TFLOP/s).  The expected cost was the weight bytes; the grouped form's rest is presumably the narrower tile (half the columns
+// per staged x row) and the 24-byte fragment path that costs the dense layer 4 - 15 %.  Recorded, not gated; no counters were taken and
+// the 128 x 128 tile was not launched.
+// The strip width of the decode form: 16, 32 and 64 columns per workgroup measured at P = 1, 4, 16, 64 on both projections (the `strip`
+// rows): 16 columns were ahead on every row (P = 1: 9.5 / 9.6 / 15.6 us at 5760 and 6.9 / 9.2 / 15.0 at 2880; P = 64: 311 / 327 / 336).
+constexpr int MX6M_PLAN_PAIRS = 32, MX6M_PLAN_PAIRS_SPARSE = 64;
+constexpr int MX6M_STRIP = 1;  // C16 of the decode form: strips of 16 columns (BIE_MXFP6_MOE_A8_STRIP = 1 / 2 / 4 under BIE_TUNING)
+
+bool mxfp6_moe_a8_decode_ok(long P) { return P >= 1 && P <= MX6M_DECODE_PAIRS; }
+bool mxfp6_moe_a8_one_launch_ok(long K) { return K <= MX6M_ONE_K; }
+
+int mxfp6_moe_a8_form(long P, long E, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP6_MOE_A8_FORM", -1);
+    if (f == 0 && P <= MX6M_DECODE_PAIRS) return 0;
+    if (f == 1) return 1;
+    return (P <= MX6M_PLAN_PAIRS || (P <= MX6M_PLAN_PAIRS_SPARSE && 2 * P <= E)) ? 0 : 1;
+}
+
+// Workspace of bie_mxfp6_moe_a8_forward, the W4A8 expert layer's: xq [R, K], xs [R, K/32], row_flag [R] for the R stored rows of x
+// (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip; every region 16-byte aligned.
+static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
+static long a6m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
+static size_t a6m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)K); }
+static size_t a6m_flag_offset(long R, long K) { return a6m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
+static size_t a6m_route_offset(long R, long K) { return a6m_flag_offset(R, K) + al16((size_t)R); }
+
+size_t mxfp6_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    return a6m_route_offset(a6m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+}
+
+template <int DT, int C16, bool FUSED>
+static void a6m_decode_launch_t(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                                const uint8_t* ecol, const void* bias, void* y, long P, int S, int E, int N, int K, int xpp, hipStream_t st) {
+    const dim3 grid((unsigned)cdivl(N, 16 * C16), (unsigned)P);
+    hipLaunchKernelGGL((mx6m_decode_kernel<DT, C16, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, S, E, N, K, xpp);
+}
+
+template <int DT, bool FUSED>
+static int a6m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
+    const int strip = BIE_KNOB("BIE_MXFP6_MOE_A8_STRIP", MX6M_STRIP);
+    if (strip >= 4) a6m_decode_launch_t<DT, 4, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else if (strip >= 2) a6m_decode_launch_t<DT, 2, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    else a6m_decode_launch_t<DT, 1, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
+    return check_launch("mx6m_decode_kernel");
+}
+
+// The contraction from quantised activations.  form 0: the routed kernel reading xq from memory (no workspace); form 1: routing into the
+// workspace (the routing region alone), then the grouped GEMM.
+int mxfp6_moe_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st) {
+    const long P = T * S;
+    if (form == 0) {
+        if (dtype == BIE_F16) return a6m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a6m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
+    if (rc) return rc;
+    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
+    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * MX6M_WN)));
+    if (dtype == BIE_F16)
+        hipLaunchKernelGGL(mx6m_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    else
+        hipLaunchKernelGGL(mx6m_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
+                           x_per_pair, max_tiles);
+    return check_launch("mx6m_gemm_kernel");
+}
+
+// The whole layer from x.  form 0 with K <= MX6M_ONE_K: one launch, the workspace is not touched.
+int mxfp6_moe_a8_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
+    const long P = T * S, R = a6m_rows(T, S, x_per_pair);
+    if (form == 0 && K <= MX6M_ONE_K) {
+        if (dtype == BIE_F16) return a6m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a6m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a6m_xs_offset(R, K);
+    uint8_t* rf = xq + a6m_flag_offset(R, K);
+    const int rc = mxfp4_a8_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
+    if (rc) return rc;
+    return mxfp6_moe_a8_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a6m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+}
+
+}  // namespace bie

@@ -786,6 +786,42 @@ int bie_mxfp6_a8_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 w6a8 mixture of experts
+ * The expert GEMM of the mxfp4 w4a8 mixture-of-experts section on stacked MXFP6 weights (the mxfp6 w6a8 section's format per expert),
+ * contracted on the block-scaled matrix instructions with an FP6 and an E4M3 operand (MXFP6A8ExpertsLinearCuda, MXFP6MoECuda;
+ * INTEGRATION.md, "MXFP6 W6A8 mixture-of-experts layer").  T, S, P, idx, x_per_pair, xq, xs, row_flag and bias are the w4a8 expert
+ * section's, unchanged.  row(p) = p / S (x_per_pair = 0) or p.
+ *   qweight  uint8 [E, N, 3K/4] (16-byte aligned): per expert and row K/32 blocks of 24 bytes, the bit order of the mxfp6 w6a8 section
+ *   scales   uint8 [E, N, K/32]; e_col uint8 [E, N] = bie_mxfp4_col_exp on the [E * N, K/32] view
+ *   y[p, n]  = dt( sum_b 2^(xs[row(p),b] + scales[e,n,b] - 254) * (sum_{k in b} e4m3(xq[row(p),k]) * e2m3(qweight[e,n,k])) + bias[e,n] ),
+ *              e = idx[p]: sums in fp32 in any order, one rounding to the dtype (0=f16 1=bf16): the mxfp6 w6a8 section's contract per pair
+ *   y[p, :]  = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255 (a NaN block of expert e reaches the pairs of e only)
+ *   y[p, :]  = +0 where idx[p] is outside [0, E): no bias and no NaN, even for a flagged row; the index is compared before any address
+ *              is formed from it
+ *   A row of y depends on its own pair only (not on the other pairs of the call nor on where the routing placed it); two runs of one
+ *   call are bit-identical.  Nothing synchronises with the host; grids are sized from P and E; expert and row offsets are 64-bit.
+ *   K % 32 == 0, 32 <= K <= 2^20; N >= 1; 1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22; dtype fp16 or bf16.
+ * bie_mxfp6_moe_a8_form: 0 = routed decode form (P <= 1024), 1 = grouped prefill form (quantise launch, routing kernel, grouped
+ *   block-scaled GEMM on 128 x 64 tiles).  The plan takes the decode form for P <= 32, and for P <= 64 while 2 P <= E (measured).  BIE_MXFP6_MOE_A8_FORM=0/1 forces a form (0 only where P <= 1024).  Host only.
+ * bie_mxfp6_moe_a8_workspace_bytes: what bie_mxfp6_moe_a8_forward needs, every region 16-byte aligned: xq, xs and row_flag of the stored
+ *   rows, then (form 1) the routing region of bie_mxfp4_moe_workspace_bytes(P, E).  form -1 gives the form-1 size, which serves either
+ *   form.  0 for a refused shape (form 0 with P > 1024 included).  Host only.
+ * bie_mxfp6_moe_a8_forward: the whole layer from x; form -1 = bie_mxfp6_moe_a8_form.  In the decode form with K <= 16384 (a row's
+ *   K + K/32 bytes of codes and scale bytes, 16896 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
+ *   pair's row itself, bit for bit as bie_mxfp8_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
+ *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight, y, workspace 16-byte aligned.
+ * bie_mxfp6_moe_a8_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq from memory and
+ *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
+ * e_col is required by every form.  Every argument is validated on the host before any device call, with the return codes of
+ * bie_mxfp4_moe_a8_forward. */
+int bie_mxfp6_moe_a8_form(long P, long E, long N, long K, int dtype);
+size_t bie_mxfp6_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form);
+int bie_mxfp6_moe_a8_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                             void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
+int bie_mxfp6_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                          const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                          int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
