@@ -161,10 +161,11 @@ TEST_HOOKS = {
     "bie_test_forge_reducer": (None, [ctypes.c_uint, _i]),
     "bie_test_forge_dependency": (None, [_i]),
     "bie_test_mpq_forward_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _sz, ctypes.POINTER(_sz)]),
+    "bie_test_mpq_gemm_plan": (_i, [_i, _i, _i] + [ctypes.POINTER(_i)] * 3),
 }
 
 _HOST_ONLY = ("bie_version", "bie_last_error", "bie_mbwq_rows", "bie_mbwq_exl2_table", "bie_status_init", "bie_device_status", "bie_test_forge_reducer",
-              "bie_test_forge_dependency", "bie_test_mpq_forward_plan", "bie_mpq_list_launches", "bie_mpq_list_form", "bie_mpq_prefill_form", "bie_mpq_rows_form", "bie_mpq_grouped_max_rows", "bie_mpq_list_destroy", "bie_mbwq_exl2_list_destroy",
+              "bie_test_forge_dependency", "bie_test_mpq_forward_plan", "bie_test_mpq_gemm_plan", "bie_mpq_list_launches", "bie_mpq_list_form", "bie_mpq_prefill_form", "bie_mpq_rows_form", "bie_mpq_grouped_max_rows", "bie_mpq_list_destroy", "bie_mbwq_exl2_list_destroy",
               "bie_ternary_conv2d_form", "bie_ternary_a8_fused_ok", "bie_mxfp4_form", "bie_mxfp4_a4_form", "bie_mxfp4_a8_form", "bie_mxfp4_moe_form", "bie_mxfp4_moe_a4_form",
               "bie_mxfp4_moe_a8_form", "bie_mxfp6_a8_form", "bie_mxfp6_moe_a8_form")
 

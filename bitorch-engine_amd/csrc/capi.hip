@@ -28,6 +28,7 @@ void test_forge_dep_set(int extra);
 // mpq_gemm.hip
 bool mpq_gemm_ok(int M, int K, int N, int w_bit, int group_size, int dtype, bool has_gidx);
 size_t mpq_gemm_workspace_bytes(int M, int K, int N);
+int mpq_gemm_plan_query(int M, int K, int N, int* BM, int* S, int* tiles_per_split);
 bool mpq_gemm_pitch_ok(int M, int K, int N, int ldy);
 // mpq_util.hip
 int mpq_dequant_launch(const int32_t* qw, const void* scales, const void* zeros, const int32_t* g_idx, void* out, int K,
@@ -269,6 +270,7 @@ int bie_test_mpq_forward_plan(int M, int K, int N, int w_bit, int group_size, in
     if (need) *need = p.workspace_bytes;
     return (int)p.form;
 }
+int bie_test_mpq_gemm_plan(int M, int K, int N, int* BM, int* S, int* tiles_per_split) { return mpq_gemm_plan_query(M, K, N, BM, S, tiles_per_split); }
 size_t bie_mpq_workspace_bytes_gidx(int M, int K, int N, int w_bit) {
     const size_t base = bie_mpq_workspace_bytes(M, K, N, w_bit);
     if (base == 0 || !gidx_dense_ok(M, K, N, BIE_F16)) return base;

@@ -519,7 +519,8 @@ struct GemmPlan {
 // without knowing dtype or bit width.
 #include "mpq_gemm_plan_table.inc"
 
-static GemmPlan plan_gemm(int M, int K, int N) {
+static GemmPlan plan_gemm(int M, int K, int N, bool* from_table = nullptr) {
+    if (from_table) *from_table = false;
     const int force_bm = BIE_KNOB("BIE_GEMM_BM", 0), force_s = BIE_KNOB("BIE_GEMM_S", 0);  // tuning knobs (tests / sweep tools)
     const int T = K / GEMM_BK;
     // Round 6: where a sweep of EVERY (BM, S) over 40 layer shapes x 11 row counts found a plan more than 2 % ahead of this model's choice
@@ -536,6 +537,7 @@ static GemmPlan plan_gemm(int M, int K, int N) {
             // up to +28 % -- profiles/r06_gemm_plan_table_holdout_nearest.txt)
             if (e != 0 && K == kPlanK[ki] && N == kPlanN[ni] && cdiv(M, BM) == cdiv(kPlanM[mi], BM) && !(BM > 32 && BM >= 2 * M) && S >= 1 && (S == 1 || T / S >= 2)) {
                 const int tps = cdiv(T, S);
+                if (from_table) *from_table = true;
                 return GemmPlan{BM, cdiv(T, tps), tps};
             }
         }
@@ -569,6 +571,17 @@ static GemmPlan plan_gemm(int M, int K, int N) {
         }
     }
     return p;
+}
+
+// the plan a fused launch of (M, K, N) takes under the current knobs, for tests (bie_test_mpq_gemm_plan): 1 a table cell's, 0 the model's
+int mpq_gemm_plan_query(int M, int K, int N, int* BM, int* S, int* tiles_per_split) {
+    if (M <= 0 || K <= 0 || N <= 0 || K % GEMM_BK) return -1;
+    bool from_table = false;
+    const GemmPlan p = plan_gemm(M, K, N, &from_table);
+    if (BM) *BM = p.BM;
+    if (S) *S = p.S;
+    if (tiles_per_split) *tiles_per_split = p.tiles_per_split;
+    return from_table ? 1 : 0;
 }
 
 static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }

@@ -19,6 +19,10 @@ void bie_test_forge_dependency(int extra);
  * workspace that kernel uses in *need (when need is not NULL).  Host only.  Returns the form: 0 the decode (lookup) kernels, 1 the inline
  * list kernel, 2 the v3 GEMV, 3 the older GEMV, 4 the fused MFMA GEMM, 5 dequantise + dense GEMM, 6 the g_idx dense form, 7 generic. */
 int bie_test_mpq_forward_plan(int M, int K, int N, int w_bit, int group_size, int dtype, int has_gidx, size_t workspace_bytes, size_t* need);
+/* The launch shape the fused MFMA GEMM takes for (M, K, N) under the current knobs (BIE_GEMM_BM, BIE_GEMM_S, BIE_GEMM_PLAN_TABLE): tile
+ * height, split-K factor and K tiles (of 64) per split, each written when its pointer is not NULL.  Host only.  Returns 1 when the plan is
+ * a cell of the measured table (csrc/mpq_gemm_plan_table.inc), 0 when the cost model chose it, negative when K % 64 != 0. */
+int bie_test_mpq_gemm_plan(int M, int K, int N, int* BM, int* S, int* tiles_per_split);
 
 #ifdef __cplusplus
 }
