@@ -135,6 +135,8 @@ SIGNATURES = {
     "bie_mxfp4_blk_exp": (_i, [_vp] * 2 + [_l] * 3 + [_vp]),
     "bie_mxfp4_linear_grad_input": (_i, [_vp] * 5 + [_l] * 3 + [_i, _vp]),
     "bie_mxfp4_moe_grad_input": (_i, [_vp] * 7 + [_l] * 5 + [_i, _i, _vp]),
+    "bie_mxfp6_linear_grad_input": (_i, [_vp] * 5 + [_l] * 3 + [_i, _vp]),
+    "bie_mxfp6_moe_grad_input": (_i, [_vp] * 7 + [_l] * 5 + [_i, _i, _vp]),
     "bie_mxfp4_moe_a4_form": (_i, [_l] * 4 + [_i]),
     "bie_mxfp4_moe_a4_workspace_bytes": (_sz, [_l] * 4 + [_i, _i]),
     "bie_mxfp4_moe_a4_forward": (_i, [_vp] * 8 + [_l] * 5 + [_i, _i, _i, _vp]),

@@ -8,12 +8,13 @@ are this library's own (include/bie_hip.h, INTEGRATION.md "MXFP6 W6A8 linear lay
   y[m, n] = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e4m3(xq) * e2m3(qweight)) + bias[n] ),  NaN for a flagged row
 
 quantize / dequant convert between a float weight and the packed pair; col_exp, quantize_act and dequant_act are the W4A8 ones (the
-scales and the activations are the same bytes); gemm contracts already-quantised activations, forward does both.  Nothing here
-synchronises with the host, so every entry can be captured in a graph."""
+scales and the activations are the same bytes); gemm contracts already-quantised activations, forward does both.  grad_input is the
+backward's gx = gy . W on the packed weight (csrc/mxfp6_grad.hip), rebiased by blk_exp's per-block-column largest scale code (the MXFP4
+one: the scale bytes are the same).  Nothing here synchronises with the host, so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip
-from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, col_exp  # noqa: F401
+from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, blk_exp, col_exp  # noqa: F401
 from bitorch_engine.extensions.mxfp4_a8_linear_cuda import _act_shape, _bias, dequant_act, quantize_act  # noqa: F401
 
 
@@ -97,3 +98,26 @@ def gemm(xq: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, qweight: to
     _hip.check(_hip.lib().bie_mxfp6_a8_gemm(_hip.ptr(xq), _hip.ptr(xs), _hip.ptr(row_flag), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col),
                                             _hip.ptr(bias), _hip.ptr(y), None, M, N, K, _hip._DT[dtype], int(form), _hip.stream()), "bie_mxfp6_a8_gemm")
     return y
+
+
+def grad_input(gy: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None) -> torch.Tensor:
+    """gy [M, N] (fp16 / bf16, any N) -> gx = gy . W [M, K] in gy's dtype, from the packed weight: no image of W is built.  e_blk
+    (blk_exp(scales)) is computed here when it is not given."""
+    _hip.need_gpu(gy, qweight, scales, e_blk)
+    if gy.dtype not in _X_DT:
+        raise RuntimeError(f"mxfp6 grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
+    N, K = _shape(qweight, scales)
+    if gy.dim() != 2 or gy.shape[1] != N:
+        raise RuntimeError(f"mxfp6 grad_input: gy {tuple(gy.shape)} does not match N={N}")
+    M = gy.shape[0]
+    gx = torch.empty((M, K), dtype=gy.dtype, device=gy.device)
+    if M == 0:
+        return gx
+    if e_blk is None:
+        e_blk = blk_exp(scales)
+    elif e_blk.dtype != torch.uint8 or e_blk.numel() != K // 32:
+        raise RuntimeError(f"mxfp6 grad_input: e_blk must be uint8 [K/32 = {K // 32}]")
+    gy, qweight, scales, e_blk = gy.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()  # held until the launch is queued
+    _hip.check(_hip.lib().bie_mxfp6_linear_grad_input(_hip.ptr(gy), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), M, N, K,
+                                                      _hip.dt(gy), _hip.stream()), "bie_mxfp6_linear_grad_input")
+    return gx

@@ -21,13 +21,25 @@ from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda
 mxfp4_experts_a8_cuda = import_extension("mxfp4_experts_a8_cuda")
 
 
-def experts_a8_backward(ext, K, ctx, gy):
+def experts_a8_backward(ext, K, ctx, gy, kernel=False):
     """The straight-through backward of an expert layer with MXFP8 activations; ext supplies dequant (the weight format's) and
-    quantize_act / dequant_act, K is the layer's input width.  Shared by the MXFP4 and the MXFP6 expert layers."""
+    quantize_act / dequant_act, K is the layer's input width.  Shared by the MXFP4 and the MXFP6 expert layers.  With kernel=True
+    grad_x is one call of ext.grad_input on the packed weights (e_blk from the scales of this call; fp32 rows summed over a token's
+    slots and rounded once when x is [T, K]) and the expert loop runs for grad_weight / grad_bias only: with neither, nothing
+    synchronises with the host."""
     x, idx, qweight, scales = ctx.saved_tensors
     E, N = qweight.shape[0], qweight.shape[1]
     T, S = idx.shape
     need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+    gxk = None
+    if need_x and kernel:
+        if x.dim() == 3:
+            gxk = ext.grad_input(gy, idx, qweight, scales).reshape(T, S, K)
+        else:
+            gxk = ext.grad_input(gy, idx, qweight, scales, out_dtype=torch.float32).reshape(T, S, K).sum(1).to(gy.dtype)
+        need_x = False
+        if not (need_w or need_b):
+            return gxk, None, None, None, None, None, None
     g = gy.reshape(T * S, N).float()
     flat = idx.reshape(-1).long()
     gx = torch.zeros((T * S, K), dtype=torch.float32, device=gy.device) if need_x else None
@@ -52,6 +64,8 @@ def experts_a8_backward(ext, K, ctx, gy):
             gb[e] = ge.sum(0)
     if need_x:
         gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
+    elif gxk is not None:
+        gx = gxk
     return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
 
 

@@ -13,7 +13,8 @@ codes are a different format, not a different packing.
 
 Training (train() with the latent weight): the weight is re-quantised on every call, the forward runs on the kernels and the backward
 is the straight-through composition in torch with the QUANTISED activations in the weight gradient.  Eval: the packed weight; a forward
-with grad enabled is differentiable in x (and bias)."""
+with grad enabled is differentiable in x (and bias).  grad_input="kernel" takes grad_x from the packed weight instead (csrc/mxfp6_grad.hip:
+no float image of W is built), in train() and in eval(); grad_weight and grad_bias stay the torch composition."""
 import math
 import typing
 
@@ -31,12 +32,14 @@ mxfp6_a8_linear_cuda = import_extension("mxfp6_a8_linear_cuda")
 class MXFP6A8LinearForward(Function):
     """Forward: the layer kernels.  Backward (straight-through estimator, in fp32 through the torch dequant, cast to the dtype):
       grad_x      = gy . W^           (identity through the activation quantiser)
+                                      (kernel: mxfp6_a8_linear_cuda.grad_input on the packed weight, e_blk from the scales of this call)
       grad_weight = gy^T . x^         (the E4M3-quantised activations)
       grad_bias   = sum_m gy"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, qweight, scales)
+        ctx.kernel = kernel
         return mxfp6_a8_linear_cuda.forward(x, qweight, scales, bias, e_col)
 
     @staticmethod
@@ -45,23 +48,30 @@ class MXFP6A8LinearForward(Function):
         x, qweight, scales = ctx.saved_tensors
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
-            grad_x = gy.float().mm(mxfp6_a8_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
+            if ctx.kernel:
+                grad_x = mxfp6_a8_linear_cuda.grad_input(gy, qweight, scales)
+            else:
+                grad_x = gy.float().mm(mxfp6_a8_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
         if ctx.needs_input_grad[1]:
             xq, xs, _ = mxfp6_a8_linear_cuda.quantize_act(x)
             grad_w = gy.float().t().mm(mxfp6_a8_linear_cuda.dequant_act(xq, xs, torch.float32)).to(gy.dtype)
         if ctx.needs_input_grad[2]:
             grad_b = gy.float().sum(0).to(gy.dtype)
-        return grad_x, grad_w, grad_b, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None
 
 
 class MXFP6A8LinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight), the
     packed codes `qweight` uint8 [N, 3K/4] and E8M0 `scales` uint8 [N, K/32] (buffers), an optional `bias` [N].
-    K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16."""
+    K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16.  grad_input: "torch" (the backward's grad_x from an fp32 image of W) or "kernel" (from
+    the packed weight)."""
 
     def __init__(self, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
-                 dtype: torch.dtype = torch.float16) -> None:
+                 dtype: torch.dtype = torch.float16, grad_input: str = "torch") -> None:
         super().__init__()
+        if grad_input not in ("torch", "kernel"):
+            raise ValueError(f'grad_input must be "torch" or "kernel" (got {grad_input!r})')
+        self.grad_input = grad_input
         if input_features % 32 or input_features <= 0 or input_features > (1 << 20) or out_features <= 0:
             raise ValueError(f"mxfp6 a8 linear needs input_features % 32 == 0, 32 <= input_features <= 2^20 and out_features >= 1 "
                              f"(got {input_features}, {out_features})")
@@ -134,5 +144,5 @@ class MXFP6A8LinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return unflatten_x(mxfp6_a8_linear_cuda.forward(x2, qweight, scales, self.bias, e_col), lead)
-        out = MXFP6A8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col)
+        out = MXFP6A8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel")
         return unflatten_x(out, lead)

@@ -13,7 +13,9 @@ the codes are a different format, not a different packing.
 
 Training (train() with the latent weight): re-quantised on every call, the forward runs on the kernels and the backward is the
 straight-through composition in torch, expert by expert, with the QUANTISED activations in the weight gradient and the identity through
-the activation quantiser in grad_x.  Eval: the packed weight; a forward with grad enabled is differentiable in x (and bias)."""
+the activation quantiser in grad_x.  Eval: the packed weight; a forward with grad enabled is differentiable in x (and bias).
+grad_input="kernel" takes grad_x from the packed weights in one grouped call (csrc/mxfp6_grad.hip: no float image of the experts is
+built and nothing synchronises with the host), in train() and in eval(); grad_weight and grad_bias stay the torch composition."""
 import math
 import typing
 
@@ -31,27 +33,33 @@ mxfp6_experts_a8_cuda = import_extension("mxfp6_experts_a8_cuda")
 class MXFP6A8ExpertsLinearForward(Function):
     """Forward: the W6A8 expert kernels.  Backward: MXFP4A8ExpertsLinearForward's straight-through composition with the MXFP6 dequant
     (grad_x through the dequantised W^[e], grad_weight[e] with the E4M3-quantised activations, grad_bias[e]; skipped slots contribute
-    nothing)."""
+    nothing).  With kernel=True grad_x is one call of mxfp6_experts_a8_cuda.grad_input on the packed weights, and the expert loop runs
+    for grad_weight / grad_bias only."""
 
     @staticmethod
-    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, idx, qweight, scales)
+        ctx.kernel = kernel
         return mxfp6_experts_a8_cuda.forward(x, idx, qweight, scales, bias, e_col)
 
     @staticmethod
     @typing.no_type_check
     def backward(ctx, gy):
-        return experts_a8_backward(mxfp6_experts_a8_cuda, ctx.saved_tensors[3].shape[2] * 32, ctx, gy)
+        return experts_a8_backward(mxfp6_experts_a8_cuda, ctx.saved_tensors[3].shape[2] * 32, ctx, gy, ctx.kernel) + (None,)
 
 
 class MXFP6A8ExpertsLinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [E, N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight),
     the packed codes `qweight` uint8 [E, N, 3K/4] and E8M0 `scales` uint8 [E, N, K/32] (buffers), an optional `bias` [E, N].
-    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16."""
+    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16.  grad_input: "torch" (the backward's grad_x from an fp32 image of every
+    expert, expert by expert) or "kernel" (from the packed weights, one grouped call)."""
 
     def __init__(self, num_experts: int, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
-                 dtype: torch.dtype = torch.float16) -> None:
+                 dtype: torch.dtype = torch.float16, grad_input: str = "torch") -> None:
         super().__init__()
+        if grad_input not in ("torch", "kernel"):
+            raise ValueError(f'grad_input must be "torch" or "kernel" (got {grad_input!r})')
+        self.grad_input = grad_input
         if input_features % 32 or input_features <= 0 or input_features > (1 << 20) or out_features <= 0 or not 1 <= num_experts <= 1024:
             raise ValueError(f"mxfp6 experts need input_features % 32 == 0, 32 <= input_features <= 2^20, out_features >= 1 and "
                              f"1 <= num_experts <= 1024 (got {input_features}, {out_features}, {num_experts})")
@@ -128,4 +136,5 @@ class MXFP6A8ExpertsLinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return mxfp6_experts_a8_cuda.forward(x, idx, qweight, scales, self.bias, e_col)
-        return MXFP6A8ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col)
+        return MXFP6A8ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col,
+                                                 self.grad_input == "kernel")

@@ -206,6 +206,10 @@ int mxfp4_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc
                             hipStream_t st);
 int mxfp4_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
                                 long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st);
+int mxfp6_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, long M, long N, long K, int dtype,
+                            hipStream_t st);
+int mxfp6_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
+                                long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -1449,6 +1453,40 @@ int bie_mxfp4_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* 
     BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(idx, 4) && !misaligned(qweight, 16) && !misaligned(gx, 16) && !misaligned(workspace, 16),
                 BIE_ERR_INVALID_ARG, "%s: qweight, gx and workspace must be 16-byte aligned, idx 4-byte, gy 2-byte aligned", fn);
     return mxfp4_moe_grad_input_launch(gy, idx, qweight, scales, e_blk, gx, workspace, P, E, N, K, dtype, out_fp32, as_stream(stream));
+}
+
+// ---- MXFP6 input gradient: the MXFP4 entries' checks on the MXFP6 weight format (bie_mxfp4_blk_exp serves both).
+int bie_mxfp6_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
+                                int dtype, void* stream) {
+    const char* fn = "bie_mxfp6_linear_grad_input";
+    int rc = check_mx(fn, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld (M >= 1 required)", fn, M);
+    BIE_REQUIRE(((M + 127) / 128) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: M=%ld, K=%ld beyond the tile count's range", fn, M, K);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(gy && qweight && scales && e_blk && gx, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
+    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(qweight, 16) && !misaligned(gx, 16), BIE_ERR_INVALID_ARG,
+                "%s: qweight and gx must be 16-byte aligned, gy 2-byte aligned", fn);
+    return mxfp6_grad_input_launch(gy, qweight, scales, e_blk, gx, M, N, K, dtype, as_stream(stream));
+}
+
+int bie_mxfp6_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
+                             void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
+    const char* fn = "bie_mxfp6_moe_grad_input";
+    int rc = check_mx(fn, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
+    BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
+    BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
+    const long P = T * S;
+    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
+                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(out_fp32 == 0 || out_fp32 == 1, BIE_ERR_INVALID_ARG, "%s: out_fp32 %d (0 = gx in the dtype, 1 = gx in fp32)", fn, out_fp32);
+    BIE_REQUIRE(gy && idx && qweight && scales && e_blk && gx && workspace, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
+    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(idx, 4) && !misaligned(qweight, 16) && !misaligned(gx, 16) && !misaligned(workspace, 16),
+                BIE_ERR_INVALID_ARG, "%s: qweight, gx and workspace must be 16-byte aligned, idx 4-byte, gy 2-byte aligned", fn);
+    return mxfp6_moe_grad_input_launch(gy, idx, qweight, scales, e_blk, gx, workspace, P, E, N, K, dtype, out_fp32, as_stream(stream));
 }
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.

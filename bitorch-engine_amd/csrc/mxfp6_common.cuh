@@ -1,8 +1,9 @@
 // The MXFP6 (OCP microscaling FP6, E2M3 elements) format's device-side rules and the W6A8 prefill tile body (gfx950): the quantiser's
 // rounding rule, code <-> fp32, a block's 24 bytes <-> its 32 codes, the FP6 operand of the block-scaled matrix instructions, and
-// mx6a8_gemm_tile on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP6 A operand (cbsz 2) and an E4M3 B operand (blgp 0).  The E8M0 block
-// scales, the block-scale rule (mx_block_scale: emax = 2 for E2M3 as for E2M1), the row sources and the MXFP8 activations are those of
-// mxfp4_common.cuh / mxfp4_a8_common.cuh.
+// mx6a8_gemm_tile on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP6 A operand (cbsz 2) and an E4M3 B operand (blgp 0), and the
+// input-gradient 128 x 128 tile body (mx6_dgrad_tile: the kernels of mxfp6_grad.hip).  The E8M0 block scales, the block-scale rule
+// (mx_block_scale: emax = 2 for E2M3 as for E2M1), the row sources and the MXFP8 activations are those of mxfp4_common.cuh /
+// mxfp4_a8_common.cuh.
 //
 // A block of 32 codes is 24 bytes: code j in bits 6 j .. 6 j + 5 of the block's little-endian 192-bit integer, which is the order in
 // which the instructions read a lane's six operand registers (tools/probe/probe_mx_fp6.hip part (a2), profiles/mxfp6_a8_probe.txt), so
@@ -244,6 +245,194 @@ __device__ __forceinline__ void mx6a8_gemm_tile(const Rows& rows, const uint8_t*
                 }
             }
     }
+}
+
+// ---- the input-gradient tile -----------------------------------------------------------------------------------------------------------------
+constexpr int MX6_DG_BM = 128, MX6_DG_BK = 128, MX6_DG_BN = 32;  // rows of gy, columns k of gx, contraction rows n of a stage
+constexpr int MX6_DG_APITCH = MX6_DG_BN * 2 + 16;                // bytes per gy row in LDS (MX_APITCH's pad)
+constexpr int MX6_DG_WPITCH = MX6_DG_BK * 2;                     // bytes per weight row n of the 16-bit image [n][k]
+constexpr int MX6_DG_STAGE = MX6_DG_BM * MX6_DG_APITCH + MX6_DG_BN * MX6_DG_WPITCH;  // 10240 + 8192
+
+// The 16-bit weight image of a stage: [32 n][128 k], 256-byte rows, the 16-byte chunk ch (8 k) of row n stored at chunk
+// ch ^ (((n & 3) << 2) | ((n >> 2) & 3)).  Every chunk stays whole and 16-byte aligned, so a lane's 8-byte transposed read (4 contiguous
+// k of one row) is 8-byte aligned and inside one chunk.  Banks, by the (a / 4) mod 64 rule (a row is 64 dwords, so the bank is 4 * the
+// stored chunk + the dword in it):
+//   transposed read (ds_read_b64_tr_b16, served per 32 lanes): a half-wave reads rows n = 4 c + q (q = 0 .. 3, c = (n >> 2) fixed) and the
+//     four chunks ch = 4 a + b (b = 0 .. 3, a fixed: 32 k of one block-column); stored chunk = ((a ^ q) << 2) | (b ^ (c & 3)): 16 distinct
+//     chunks for the 16 (q, b), two lanes (the 8-byte halves) in each: all 64 banks, no conflict.
+//   write (ds_write_b128, served per 8 consecutive lanes, bank mod 32 = the stored chunk mod 8): the 8 lanes hold the blocks
+//     kb = 2 a1 + a0 with a0 = lane bit 0 and rows n with (n >> 2) & 3 = lane bits 1, 2, n & 3 fixed; chunk 4 kb + c is stored at
+//     ((a0 ^ (n & 1)) << 2 | (c ^ ((n >> 2) & 3))) mod 8: 8 distinct values, no conflict.
+__device__ __forceinline__ int mx6_dg_woff(int n, int ch) { return n * MX6_DG_WPITCH + ((ch ^ (((n & 3) << 2) | ((n >> 2) & 3))) << 4); }
+
+// one block's 32 codes -> 32 16-bit values at one scale (v_cvt_scalef32_pk32_{bf16,f16}_fp6: element j of the result is code j,
+// tools/probe/probe_fp6_cvt.hip part (a)), as four 16-byte chunks of 8 k; and the transposed LDS read of 4 rows of one column
+typedef uint32_t mx6_v6u __attribute__((ext_vector_type(6)));
+typedef uint32_t mx6_v16u __attribute__((ext_vector_type(16)));
+typedef short mx6_short4_t __attribute__((ext_vector_type(4)));
+typedef short mx6_short8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 mx6_bf16x32_t __attribute__((ext_vector_type(32)));
+typedef _Float16 mx6_half32_t __attribute__((ext_vector_type(32)));
+__device__ __forceinline__ mx6_short8_t mx6_tr2(const unsigned char* p0, const unsigned char* p1) {  // two ds_read_b64_tr_b16
+    typedef __attribute__((address_space(3))) mx6_short4_t* lp;
+    const mx6_short4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)p0), b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)p1);
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+template <int DT> struct mx6_dg;
+template <> struct mx6_dg<BIE_BF16> {
+    static __device__ __forceinline__ mx6_v16u cvt(const mx6_v6u& w, float s) {
+        return __builtin_bit_cast(mx6_v16u, __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(w, s));
+    }
+    static __device__ __forceinline__ mx_bf16x8_t tr2(const unsigned char* p0, const unsigned char* p1) { return __builtin_bit_cast(mx_bf16x8_t, mx6_tr2(p0, p1)); }
+};
+template <> struct mx6_dg<BIE_F16> {
+    static __device__ __forceinline__ mx6_v16u cvt(const mx6_v6u& w, float s) {
+        return __builtin_bit_cast(mx6_v16u, __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(w, s));
+    }
+    static __device__ __forceinline__ mx_half8_t tr2(const unsigned char* p0, const unsigned char* p1) { return __builtin_bit_cast(mx_half8_t, mx6_tr2(p0, p1)); }
+};
+
+// One 128 x 128 tile of gx = gy . W on v_mfma_f32_32x32x16_{bf16,f16}, contracted over the N MXFP6 weight rows that start at row r0 of
+// qw / sc (0, or (long)e * N for expert e): mx_dgrad_tile's contract (mxfp4_common.cuh) with E2M3 elements.  Tile rows from `rows` (a
+// live row reads gy[src] and writes gx[dst]), columns k0 .. of K, rebiased by eblk[k / 32] (the caller's pointer already at the
+// expert's K / 32 codes).  ODT, the element type of gx, is DT or BIE_F32.  4 waves as 2 x 2, wave tile 64 x 64.
+// Per stage of 32 n a thread loads 2 x 16 bytes of gy, and the lower half of every wave one block (n, kb) of the stage's 32 x 4: its
+// 24 bytes in three 8-byte pieces (a block is only 8-byte aligned) and its scale byte, into registers while the MFMAs run on the other
+// LDS buffer.  It then converts the block with ONE v_cvt_scalef32_pk32 at 2^(s[n, kb] - e_blk[kb]) and writes the 64 bytes as four
+// chunks of the 16-bit image (mx6_dg_woff).  Lane (r = lane & 31, h = lane >> 5) of a 16-n step reads its B fragment, rows 8 h .. + 7
+// of column r of a 32-column block, with two ds_read_b64_tr_b16 (rows .. + 3 and + 4 .. + 7): lane 4 q + p of a 16-lane group gives the
+// address of row q, columns 4 p .. + 3, of the group's 4 x 16 block and receives column (lane & 15).  Every lane of every wave gives an
+// in-bounds address (the image is always whole: rows past N and blocks past K are written as zeros), the loops are uniform and there
+// is no return before them, so EXEC is all ones at the transposed reads.  The accumulators acc[.][j] hold column 32 j + r in lane r;
+// before the epilogue the lanes of a pair (r even, r + 1) swap one value each, so that lane r even holds columns r, r + 1 and lane r
+// odd 32 + r - 1, 32 + r, and the epilogue is mx_dgrad_tile's: two adjacent columns in one store.  gy rows have any length N: whole
+// 16-byte pieces where `vec` (N % 8 == 0 and gy 16-byte aligned), else 16-bit loads, each guarded by n < N.  Dead rows and whatever
+// lies past N / K: gy and codes load as zero, the scale as 1.0, so the padding adds exact zeros.  gy rows in LDS: 80-byte pitch, the
+// 16-byte slot of row r is 5 r mod 16, distinct over each 16-lane group of the ds_read_b128 fragment reads ({0-3, 12-15, 20-27} and
+// {4-11, 16-19, 28-31} of a half-wave).  The gy WRITES are 2-way on one bank quad: the 8 lanes of a ds_write_b128 group hold the four
+// pieces of two rows, banks 20 r + 4 c mod 32, and piece 3 of the odd row meets piece 0 of the even one.  Counters show exactly that
+// and nothing else (profiles/mxfp6_grad_pmc.txt: 16 conflict cycles per wave and stage, none with the write order changed to 8 rows
+// of one piece per group); that order was measured slower all the same (its global loads put neighbouring lanes on different rows),
+// so the staging order of mx_dgrad_tile stays.  All 256 threads of the workgroup must call it together.
+template <int DT, int ODT, class Rows>
+__device__ __forceinline__ void mx6_dgrad_tile(const Rows& rows, const uint16_t* __restrict__ gy, const uint8_t* __restrict__ qw,
+                                               const uint8_t* __restrict__ sc, const uint8_t* __restrict__ eblk, void* __restrict__ gx, long r0,
+                                               int k0, int N, int K, bool vec) {
+    typedef mx_frag<DT> F;
+    typedef mx6_dg<DT> G;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX6_DG_STAGE];
+    constexpr int W_OFF = MX6_DG_BM * MX6_DG_APITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int NT = (N + MX6_DG_BN - 1) / MX6_DG_BN, KB = K >> 5;
+
+    // this thread's load slots.  Weight block: w = 32 wave + lane (lane < 32); block-column wkb = w bits 0 and 3, row wn = w bits 4, 5
+    // (n & 3), bits 1, 2 ((n >> 2) & 3) and bit 6 (n >> 4): the order the image's write banks want (mx6_dg_woff)
+    const bool wt = lane < 32;
+    const int w = wave * 32 + (lane & 31);
+    const int wkb = (w & 1) | ((w >> 2) & 2), wn = ((w >> 4) & 3) | (((w >> 1) & 3) << 2) | (((w >> 6) & 1) << 4);
+    const bool wk_ok = wt && (k0 >> 5) + wkb < KB;
+    const uint8_t* wsrc = qw + r0 * ((long)KB * MX6_BLOCK_BYTES) + (long)((k0 >> 5) + wkb) * MX6_BLOCK_BYTES;
+    const uint8_t* ssrc = sc + r0 * KB + (k0 >> 5) + wkb;
+    const uint32_t eb = wk_ok ? eblk[(k0 >> 5) + wkb] : 0u;
+    const uint16_t* grow[2];  // the gy rows of this thread's two 16-byte pieces per stage: tile row (t + 256 i) / 4, piece t & 3
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int row = (t + 256 * i) >> 2;
+        grow[i] = rows.live(row) ? gy + rows.src(row) * N : nullptr;
+    }
+    uint4_t ra[2];
+    uint2_t rw[3];
+    float rs;
+    auto load = [&](int nt) {
+        const int na = nt * MX6_DG_BN + (t & 3) * 8;  // the first n of this thread's pieces
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            if (!grow[i] || na >= N) {
+                ra[i] = uint4_t{0u, 0u, 0u, 0u};
+            } else if (vec) {  // uniform; N % 8 == 0: the piece lies inside the row
+                ra[i] = *reinterpret_cast<const uint4_t*>(grow[i] + na);
+            } else {
+                uint32_t h[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) h[j] = na + j < N ? (uint32_t)grow[i][na + j] : 0u;
+                ra[i] = uint4_t{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+            }
+        }
+        const int n = nt * MX6_DG_BN + wn;
+        const bool ok = wk_ok && n < N;
+        const uint2_t* src = reinterpret_cast<const uint2_t*>(wsrc + (long)n * ((long)KB * MX6_BLOCK_BYTES));
+#pragma unroll
+        for (int i = 0; i < 3; i++) rw[i] = ok ? src[i] : uint2_t{0u, 0u};
+        rs = ok ? mx_rebias(ssrc[(long)n * KB], eb) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX6_DG_STAGE;
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int q = t + 256 * i, row = q >> 2, c16 = q & 3;
+            *reinterpret_cast<uint4_t*>(st + row * MX6_DG_APITCH + c16 * 16) = ra[i];
+        }
+        const mx6_v16u v = G::cvt(mx6_v6u{rw[0].x, rw[0].y, rw[1].x, rw[1].y, rw[2].x, rw[2].y}, rs);
+        if (wt) {
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                *reinterpret_cast<uint4_t*>(st + W_OFF + mx6_dg_woff(wn, wkb * 4 + c)) = uint4_t{v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
+        }
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    // the transposed reads of this lane: row tq of its group's 4-row block, the 8-byte half tp & 1 of chunk tch (+ 4 j + 8 wx)
+    const int tq = (lane >> 2) & 3, tp = lane & 3, tch = wx * 8 + ((lane >> 4) & 1) * 2 + (tp >> 1);
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int nt = 0; nt < NT; nt++) {
+        const int buf = nt & 1;
+        if (nt + 1 < NT) load(nt + 1);
+        const unsigned char* st = lds + buf * MX6_DG_STAGE;
+#pragma unroll
+        for (int ns = 0; ns < MX6_DG_BN / 16; ns++) {
+            typename F::t a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX6_DG_APITCH + ns * 32 + hh * 16));
+            const int n0 = ns * 16 + hh * 8 + tq;
+#pragma unroll
+            for (int j = 0; j < 2; j++)
+                b[j] = G::tr2(st + W_OFF + mx6_dg_woff(n0, tch + 4 * j) + (tp & 1) * 8, st + W_OFF + mx6_dg_woff(n0 + 4, tch + 4 * j) + (tp & 1) * 8);
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+        }
+        if (nt + 1 < NT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: acc[i][j][r] is column 32 j + rl of the wave's 64, tile row (r & 3) + 8 (r >> 2) + 4 hh.  The lanes of a pair swap: the even
+    // lane gives its column 32 + rl and takes the odd lane's column rl + 1, so v0, v1 are two adjacent columns from kc on
+    const bool odd = (rl & 1) != 0;
+    const int k = k0 + wx * 64 + (odd ? 32 + rl - 1 : rl);
+    const bool k_ok = k < K;  // K % 32 == 0 and k is even: the pair lies inside K or outside
+    const float cs = e8m0_f32(eblk[k_ok ? k >> 5 : 0]);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float give = odd ? acc[i][0][r] : acc[i][1][r];
+            const float take = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(give), 0xB1, 0xf, 0xf, false));  // quad_perm [1, 0, 3, 2]
+            const float v0 = odd ? take : acc[i][0][r], v1 = odd ? acc[i][1][r] : take;
+            const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (k_ok && rows.live(row)) mx_store2<ODT>(gx, rows.dst(row) * K + k, v0 * cs, v1 * cs);
+        }
 }
 
 }  // namespace bie

@@ -822,6 +822,31 @@ int bie_mxfp6_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* r
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 input gradient
+ * gx = gy . W straight from the packed weights of the mxfp6 w6a8 and mxfp6 w6a8 mixture-of-experts sections, for the backward of their
+ * layers ("MXFP6 input gradient"): the mxfp4 input gradient's contract with E2M3 elements.  qweight / scales are those
+ * sections', unchanged (a block of qweight is only 8-byte aligned).
+ *   gx[m, k] = odt( sum_n gy[m, n] * W[n, k] ),  W[n, k] = e2m3(code) * 2^(scales[n, k/32] - 127): products exact, the sum in fp32 in an
+ *            order fixed by N alone, one rounding
+ *   e_blk    uint8 [K/32] ([E, K/32]) = bie_mxfp4_blk_exp(scales) (the scale bytes are the mxfp4 section's).  The kernels rebias by it: a
+ *            block-column with e_blk == 255 is NaN in every row of gx.  In fp16 a block whose scale code is up to 11 below its
+ *            block-column's largest is held in normal fp16 numbers (the smallest E2M3 magnitude is 2^-3); from 12 to 21 below, its
+ *            values are fp16 subnormals that are still exact (multiples of 2^-24), which the convert and the matrix instruction keep
+ *            on gfx950 (profiles/mxfp6_grad_probe.txt); from 22 below bits are lost and from 28 below the block is zero.  In bf16 every
+ *            bit is kept down to 123 below; 124 .. 126 below are bf16 subnormals (unspecified), and beyond that the block is zero.
+ *   K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1 (gy rows need no alignment beyond 2 bytes); dtype fp16 or bf16.
+ * bie_mxfp6_linear_grad_input: gy [M, N] and gx [M, K] (16-byte aligned) in the dtype.
+ * bie_mxfp6_moe_grad_input: gy [P, N] (one row per pair, P = T * S), idx int32 [T, S], gx [P, K] in the dtype (out_fp32 = 0) or in fp32
+ *   (out_fp32 = 1); gx[p, :] = gy[p] . W[idx[p]], 0 where idx[p] is outside [0, E), and nothing is read through such an index.  A row of
+ *   gx depends on its own pair only.  workspace: bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned, need not be initialised.
+ *   1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22.
+ * One form each (a 128 x 128 tile GEMM on the matrix instructions): a small M is correct, not efficient.  Every argument is validated
+ * on the host before any device call, with the return codes of the mxfp4 entries; nothing synchronises with the host. */
+int bie_mxfp6_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
+                                int dtype, void* stream);
+int bie_mxfp6_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
+                             void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
