@@ -12,3 +12,4 @@ from .mxfp4_moe_layer import MXFP4MoECuda
 from .mxfp6_a8_layer import MXFP6A8LinearCuda, MXFP6A8LinearForward
 from .mxfp6_experts_a8_layer import MXFP6A8ExpertsLinearCuda, MXFP6A8ExpertsLinearForward
 from .mxfp6_moe_layer import MXFP6MoECuda
+from .mxfp6_layer import MXFP6LinearCuda, MXFP6LinearForward

@@ -183,6 +183,13 @@ int mxfp6_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* ro
 int mxfp6_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st);
 
+// mxfp6.hip
+int mxfp6_form(long M, long N, long K, int dtype);
+bool mxfp6_decode_ok(long M);
+int mxfp6_decode_rows();
+int mxfp6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
+                         int dtype, int form, hipStream_t st);
+
 // mxfp6_moe_a8.hip
 int mxfp6_moe_a8_form(long P, long E, long N, long K, int dtype);
 bool mxfp6_moe_a8_decode_ok(long P);
@@ -1212,6 +1219,22 @@ int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_f
     BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
                 "bie_mxfp6_a8_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
     return mxfp6_a8_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+}
+
+// ---- MXFP6 weight-only (W6A16).  Everything is checked here, before any device call; the shape limits are the MXFP4 layer's.
+int bie_mxfp6_form(long M, long N, long K, int dtype) { return mxfp6_form(M, N, K, dtype); }
+
+int bie_mxfp6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                             long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mxa4("bie_mxfp6_linear_forward", M, N, K, dtype);
+    if (rc) return rc;
+    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "bie_mxfp6_linear_forward: form %d (-1 = plan, 0 = decode, 1 = prefill)", form);
+    if (form < 0) form = mxfp6_form(M, N, K, dtype);
+    BIE_REQUIRE(form == 1 || mxfp6_decode_ok(M), BIE_ERR_UNSUPPORTED, "bie_mxfp6_linear_forward: the decode form takes M <= %d (M=%ld)", mxfp6_decode_rows(), M);
+    BIE_REQUIRE(x && qweight && scales && y && (form == 0 || e_col), BIE_ERR_INVALID_ARG, "bie_mxfp6_linear_forward: NULL tensor pointer (the prefill form needs e_col)");
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(y, 2) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mxfp6_linear_forward: x and qweight must be 16-byte aligned, y and bias 2-byte aligned");
+    return mxfp6_forward_launch(x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
 }
 
 // ---- MXFP4 mixture of experts.  Everything is checked here, before any device call.

@@ -1,7 +1,8 @@
 // The MXFP6 (OCP microscaling FP6, E2M3 elements) format's device-side rules and the W6A8 prefill tile body (gfx950): the quantiser's
 // rounding rule, code <-> fp32, a block's 24 bytes <-> its 32 codes, the FP6 operand of the block-scaled matrix instructions, and
 // mx6a8_gemm_tile on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP6 A operand (cbsz 2) and an E4M3 B operand (blgp 0), and the
-// input-gradient 128 x 128 tile body (mx6_dgrad_tile: the kernels of mxfp6_grad.hip).  The E8M0 block scales, the block-scale rule
+// input-gradient 128 x 128 tile body (mx6_dgrad_tile: the kernels of mxfp6_grad.hip), and the weight-only (W6A16) 128 x 128 tile body
+// (mx6_gemm_tile: mx6_gemm_kernel of mxfp6.hip).  The E8M0 block scales, the block-scale rule
 // (mx_block_scale: emax = 2 for E2M3 as for E2M1), the row sources and the MXFP8 activations are those of mxfp4_common.cuh /
 // mxfp4_a8_common.cuh.
 //
@@ -433,6 +434,184 @@ __device__ __forceinline__ void mx6_dgrad_tile(const Rows& rows, const uint16_t*
             const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
             if (k_ok && rows.live(row)) mx_store2<ODT>(gx, rows.dst(row) * K + k, v0 * cs, v1 * cs);
         }
+}
+
+// The pk32 convert's native result (32 16-bit values) and its pieces, for the forms that keep it in registers.  The pieces are taken
+// element by element from the native vector: taking dwords out of a bit cast to mx6_v16u is folded by the compiler (ROCm 7 clang) to
+// dword 0 for every index where the dwords feed arithmetic directly (mx6_dg::cvt, whose result is stored whole, is not affected).
+template <int DT> struct mx6_w16;
+template <> struct mx6_w16<BIE_BF16> {
+    typedef mx6_bf16x32_t t;
+    static __device__ __forceinline__ t cvt(const mx6_v6u& w, float s) { return __builtin_amdgcn_cvt_scalef32_pk32_bf16_fp6(w, s); }
+    static __device__ __forceinline__ bf16x2_t pair(const t& v, int i) { return bf16x2_t{v[2 * i], v[2 * i + 1]}; }
+    static __device__ __forceinline__ mx_bf16x8_t chunk(const t& v, int c) {
+        return mx_bf16x8_t{v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6], v[8 * c + 7]};
+    }
+};
+template <> struct mx6_w16<BIE_F16> {
+    typedef mx6_half32_t t;
+    static __device__ __forceinline__ t cvt(const mx6_v6u& w, float s) { return __builtin_amdgcn_cvt_scalef32_pk32_f16_fp6(w, s); }
+    static __device__ __forceinline__ half2_t pair(const t& v, int i) { return half2_t{v[2 * i], v[2 * i + 1]}; }
+    static __device__ __forceinline__ mx_half8_t chunk(const t& v, int c) {
+        return mx_half8_t{v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6], v[8 * c + 7]};
+    }
+};
+
+// ---- the weight-only (W6A16) prefill tile ----------------------------------------------------------------------------------------------------
+constexpr int MX6_BK = 64;                             // k per stage: two blocks, 48 code bytes per weight row
+constexpr int MX6_WROW = MX6_BK / 32 * MX6_BLOCK_BYTES;  // 48
+// 56 bytes per weight row in LDS (14 dwords).  A lane's block is the 24 bytes at row * 56 + 24 * block, three 8-byte reads.  The lanes
+// of a half-wave read the same block of rows r = 0 .. 31: per piece the dwords 14 r + c and 14 r + c + 1.  By the rule above: as
+// ds_read_b64 (per 32 lanes, bank = dword mod 64), 14 r mod 64 = 2 (7 r mod 32) takes 32 distinct even values, so the 32 dword pairs
+// tile all 64 banks; as ds_read2_b64 (per 16 lanes, bank = dword mod 32), 14 r mod 32 = 2 (7 r mod 16) takes 16 distinct even values.
+// Counters (profiles/mxfp6_pmc.txt): 16 bank-conflict cycles per wave and stage against 8 for mx_gemm_tile in the same run; the 8 more are
+// what the packed WRITES predict (a half-wave's 32 consecutive 8-byte pieces span 74 or 76 dwords), 3 % of a stage's matrix time.
+constexpr int MX6_WPITCH = MX6_WROW + 8;
+constexpr int MX6_STAGE = MX_BM * MX_APITCH + MX_BN * MX6_WPITCH + MX_BN * 2 * 4;  // x (mx_gemm_tile's rows), codes, two fp32 rebiased scales per row
+
+// One 128 x 128 tile of y = x . W^T (+ bias) on v_mfma_f32_32x32x16_{bf16,f16}: mx_gemm_tile's contract and structure (mxfp4_common.cuh)
+// with MXFP6 weights.  Tile rows from `rows`, columns n0 .. of the N weight rows that start at row r0 of qw / sc / ecol / bias (0, or
+// (long)e * N for an expert e).  4 waves as 2 x 2, wave tile 64 x 64.  Per 64-k stage a thread loads 4 x 16 bytes of x, three 8-byte
+// pieces of codes (a weight row's pitch is 24 K / 32 bytes: nothing wider is aligned) and one scale byte into registers while the
+// MFMAs run on the other LDS buffer, then writes them (the scale already rebiased to fp32 by e_col).  The weight tile is staged
+// PACKED.  The contraction order inside a stage is free, so lane (n = lane & 31, h = lane >> 5) reads block h of weight row n, turns
+// its 32 codes into 32 16-bit values with ONE v_cvt_scalef32_pk32 at 2^(s - e_col[n]) (element j = code j, probe_fp6_cvt.hip part (a)),
+// and uses the four 8-k chunks as the B fragments of four MFMAs; the A fragment of MFMA i is then x at k = 32 h + 8 i .. + 7 of the
+// stage.  No transposed read and no 16-bit image of W in LDS.  The x reads are 16 bytes at row * 144 + 64 h + 16 i: a 16-lane group of
+// the ds_read_b128 reads 16 consecutive rows at one offset, and the 16-byte slot of row r is 9 r + c mod 16: 16 distinct slots (mx_gemm_tile's
+// pad, unchanged).  Dead rows and whatever lies past N / K: x and
+// codes load as zero, scales as 1.0, so the padding adds exact zeros.  All 256 threads of the workgroup must call it together.
+template <int DT, class Rows>
+__device__ __forceinline__ void mx6_gemm_tile(const Rows& rows, const uint16_t* __restrict__ x, const uint8_t* __restrict__ qw,
+                                              const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol, const void* __restrict__ bias,
+                                              void* __restrict__ y, long r0, int n0, int N, int K) {
+    typedef mx_frag<DT> F;
+    typedef mx6_w16<DT> G;
+    static_assert(2 * MX6_STAGE <= 65536, "static LDS");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX6_STAGE];
+    constexpr int W_OFF = MX_BM * MX_APITCH, S_OFF = W_OFF + MX_BN * MX6_WPITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int KT = (K + MX6_BK - 1) / MX6_BK, KB = K >> 5;
+
+    // this thread's load slots: code pieces t, t + 256, t + 512 of the tile's 128 x 6 (row = piece / 6, 8-byte piece % 6 of the row's 48
+    // bytes: block (piece % 6) / 3 of the stage); the scale of row t >> 1, block t & 1
+    const uint8_t* wsrc[3];
+    bool wok[3];
+    int wblk[3], wdst[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int p = t + 256 * i, row = p / 6, part = p - row * 6;
+        wblk[i] = part / 3;
+        wdst[i] = W_OFF + row * MX6_WPITCH + part * 8;
+        wok[i] = n0 + row < N;
+        wsrc[i] = qw + (r0 + min(n0 + row, N - 1)) * ((long)KB * MX6_BLOCK_BYTES) + part * 8;
+    }
+    const int bn = t >> 1, bh = t & 1;
+    const int nb = n0 + bn;
+    const bool nb_ok = nb < N;
+    const uint8_t* ssrc = sc + (r0 + min(nb, N - 1)) * KB + bh;
+    const uint32_t e = nb_ok ? ecol[r0 + nb] : 0u;
+    const uint16_t* xrow[4];  // the x rows of this thread's four 16-byte pieces per stage: tile row (t + 256 i) / 8, piece t & 7
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = (t + 256 * i) >> 3;
+        xrow[i] = rows.live(row) ? x + rows.src(row) * K + (t & 7) * 8 : nullptr;
+    }
+    uint4_t ra[4];
+    uint2_t rw[3];
+    float rs;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            ra[i] = (xrow[i] && kt * MX6_BK + (t & 7) * 8 < K) ? *reinterpret_cast<const uint4_t*>(xrow[i] + kt * MX6_BK) : uint4_t{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+            rw[i] = (wok[i] && kt * 2 + wblk[i] < KB) ? __builtin_nontemporal_load(reinterpret_cast<const uint2_t*>(wsrc[i] + (long)kt * MX6_WROW))
+                                                      : uint2_t{0u, 0u};
+        rs = (nb_ok && kt * 2 + bh < KB) ? mx_rebias(__builtin_nontemporal_load(ssrc + kt * 2), e) : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX6_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MX_APITCH + c16 * 16) = ra[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) *reinterpret_cast<uint2_t*>(st + wdst[i]) = rw[i];
+        reinterpret_cast<float*>(st + S_OFF)[bn * 2 + bh] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * MX6_STAGE;
+        const float* ss = reinterpret_cast<const float*>(st + S_OFF);
+        typename G::t bv[2];  // block hh of the wave's weight rows 32 j + rl: 32 values, k 32 hh .. + 31 of the stage
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int n = wx * 64 + j * 32 + rl;
+            const uint2_t* p = reinterpret_cast<const uint2_t*>(st + W_OFF + n * MX6_WPITCH + hh * MX6_BLOCK_BYTES);
+            const uint2_t p0 = p[0], p1 = p[1], p2 = p[2];
+            bv[j] = G::cvt(mx6_v6u{p0.x, p0.y, p1.x, p1.y, p2.x, p2.y}, ss[n * 2 + hh]);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) {
+            typename F::t a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX_APITCH + hh * 64 + ks * 16));
+#pragma unroll
+            for (int j = 0; j < 2; j++) b[j] = G::chunk(bv[j], ks);
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) acc[i][j] = F::mfma(a[i], b[j], acc[i][j]);
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: column n = lane & 31, tile row (r & 3) + 8 (r >> 2) + 4 hh.  e_col = 255 (a NaN block in the column) makes cs NaN
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int n = n0 + wx * 64 + j * 32 + rl;
+        if (n >= N) continue;
+        const float cs = e8m0_f32(ecol[r0 + n]);
+        const float bv0 = bias ? dt_traits<DT>::load(bias, r0 + n) : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (rows.live(row)) {
+                    float v = acc[i][j][r] * cs;
+                    if (bias) v += bv0;
+                    dt_traits<DT>::store(y, rows.dst(row) * N + n, v);
+                }
+            }
+    }
+}
+
+// the sums of a wave's two halves on the DPP network (wave_sum_f32's first five steps): lane 31 holds lanes 0 .. 31, lane 63 lanes 32 .. 63
+__device__ __forceinline__ float mx6_half_sum_f32(float v) {
+    v = dpp_add<0xB1, 0xf>(v);
+    v = dpp_add<0x4E, 0xf>(v);
+    v = dpp_add<0x141, 0xf>(v);
+    v = dpp_add<0x140, 0xf>(v);
+    return dpp_add<0x142, 0xa>(v);
 }
 
 }  // namespace bie

@@ -786,6 +786,24 @@ int bie_mxfp6_a8_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 (w6a16)
+ * MXFP6 weights (the mxfp6 w6a8 section's qweight / scales, byte for byte) against fp16 / bf16 activations: the mxfp4 section's contract
+ * with E2M3 elements (MXFP6LinearCuda; INTEGRATION.md, "MXFP6 linear layer").  The semantics are defined by this library:
+ *   W[n, k]  = e2m3(code) * 2^(s - 127)   (exact in fp32)
+ *   y[m, n]  = dt( sum_k x[m, k] * W[n, k] + bias[n] ): products exact, the sum in fp32 in any order, one rounding to the dtype (0=f16 1=bf16)
+ *   K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.  A column n with a scale-255 block is NaN in every row; a scale-0 block is 2^-127 and
+ *   may flush to zero.  Non-finite x goes through the products by IEEE rules; no row affects another row.
+ * bie_mxfp6_form: 0 = decode form (exists for M <= 32), 1 = prefill form (MFMA GEMM).  The plan takes the decode form for M <= 32
+ *   (measured); BIE_MXFP6_FORM=0/1 forces one (0 only where the decode form exists).  Host only.
+ * bie_mxfp6_linear_forward: x [M, K] (16-byte aligned), bias [N] in the dtype or NULL, y [M, N]; e_col of bie_mxfp4_col_exp (the
+ *   prefill form reads it; the decode form takes NULL); form -1 = bie_mxfp6_form.  The decode form keeps the fp32 range of W; the prefill
+ *   form holds e2m3 * 2^(s - e_col[n]) in 16 bits, so within a column a block more than 2^-24 (fp16) below the column's largest scale
+ *   loses bits below that column's fp16 subnormal step.  Form 0 with M > 32: BIE_ERR_UNSUPPORTED.
+ * Every argument is validated on the host before any device call; nothing allocates or synchronises with the host (graph-capturable). */
+int bie_mxfp6_form(long M, long N, long K, int dtype);
+int bie_mxfp6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                             long N, long K, int dtype, int form, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp6 w6a8 mixture of experts
  * The expert GEMM of the mxfp4 w4a8 mixture-of-experts section on stacked MXFP6 weights (the mxfp6 w6a8 section's format per expert),
  * contracted on the block-scaled matrix instructions with an FP6 and an E4M3 operand (MXFP6A8ExpertsLinearCuda, MXFP6MoECuda;
