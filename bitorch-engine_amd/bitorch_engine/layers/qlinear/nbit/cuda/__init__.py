@@ -11,5 +11,6 @@ from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda, MXFP4A8ExpertsLine
 from .mxfp4_moe_layer import MXFP4MoECuda
 from .mxfp6_a8_layer import MXFP6A8LinearCuda, MXFP6A8LinearForward
 from .mxfp6_experts_a8_layer import MXFP6A8ExpertsLinearCuda, MXFP6A8ExpertsLinearForward
-from .mxfp6_moe_layer import MXFP6MoECuda
+from .mxfp6_experts_layer import MXFP6ExpertsLinearCuda, MXFP6ExpertsLinearForward
+from .mxfp6_moe_layer import MXFP6MoECuda, MXFP6A16MoECuda
 from .mxfp6_layer import MXFP6LinearCuda, MXFP6LinearForward

@@ -207,6 +207,11 @@ bool mxfp4_moe_decode_ok(long P);
 size_t mxfp4_moe_workspace_bytes(long P, long E);
 int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                              void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
+// mxfp6_moe.hip
+int mxfp6_moe_form(long P, long E, long N, long K, int dtype);
+bool mxfp6_moe_decode_ok(long P);
+int mxfp6_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                             void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
 // mxfp4_grad.hip
 int mxfp4_blk_exp_launch(const uint8_t* sc, uint8_t* eblk, long rows, long K, long groups, hipStream_t st);
 int mxfp4_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, long M, long N, long K, int dtype,
@@ -1267,6 +1272,34 @@ int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qwei
                     (form == 0 || !misaligned(workspace, 16)),
                 BIE_ERR_INVALID_ARG, "%s: x, qweight and workspace must be 16-byte aligned, idx 4-byte, y and bias 2-byte aligned", fn);
     return mxfp4_moe_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+}
+
+// ---- MXFP6 weight-only (W6A16) mixture of experts: bie_mxfp4_moe_forward's checks line for line, the workspace bie_mxfp4_moe_workspace_bytes.
+int bie_mxfp6_moe_form(long P, long E, long N, long K, int dtype) { return mxfp6_moe_form(P, E, N, K, dtype); }
+
+int bie_mxfp6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    const char* fn = "bie_mxfp6_moe_forward";
+    int rc = check_mx(fn, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
+    BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
+    BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
+    const long P = T * S;
+    BIE_REQUIRE(N <= (1L << 31) - 128, BIE_ERR_UNSUPPORTED, "%s: N=%ld beyond 2^31 - 128 (the column tiles are counted in int)", fn, N);
+    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((N + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
+                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
+    BIE_REQUIRE(x_per_pair == 0 || x_per_pair == 1, BIE_ERR_INVALID_ARG, "%s: x_per_pair %d (0 = x is [T, K], 1 = x is [P, K])", fn, x_per_pair);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, form);
+    if (form < 0) form = mxfp6_moe_form(P, E, N, K, dtype);
+    BIE_REQUIRE(form == 1 || mxfp6_moe_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
+    BIE_REQUIRE(x && idx && qweight && scales && y && (form == 0 || (e_col && workspace)), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (the prefill form needs e_col and the workspace)", fn);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 2) && !misaligned(bias, 2) &&
+                    (form == 0 || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: x, qweight and workspace must be 16-byte aligned, idx 4-byte, y and bias 2-byte aligned", fn);
+    return mxfp6_moe_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
 }
 
 // ---- MXFP4 W4A4 mixture of experts.  Everything is checked here, before any device call.

@@ -150,13 +150,6 @@ int mxfp6_form(long M, long N, long K, int dtype) {
 bool mxfp6_decode_ok(long M) { return M >= 1 && M <= MX6_DECODE_ROWS; }
 int mxfp6_decode_rows() { return MX6_DECODE_ROWS; }
 
-// threads per column group: the largest of 128, 64, 32 whose padded last pass wastes at most an eighth of the passes' slots, else 32
-static int mx6_decode_group(int KB) {
-    for (int g = 128; g > 32; g >>= 1)
-        if ((long)cdiv(KB, g) * g * 8 <= (long)KB * 9) return g;
-    return 32;
-}
-
 template <int DT, int R, int G>
 static void mx6_decode_launch_g(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
     constexpr int CT = (G == 32 || R >= 32) ? 2 : 4, C = CT * (256 / G);

@@ -614,4 +614,12 @@ __device__ __forceinline__ float mx6_half_sum_f32(float v) {
     return dpp_add<0x142, 0xa>(v);
 }
 
+// (host; shared by the decode forms of mxfp6.hip and mxfp6_moe.hip)
+// threads per column group: the largest of 128, 64, 32 whose padded last pass wastes at most an eighth of the passes' slots, else 32
+static int mx6_decode_group(int KB) {
+    for (int g = 128; g > 32; g >>= 1)
+        if ((long)cdiv(KB, g) * g * 8 <= (long)KB * 9) return g;
+    return 32;
+}
+
 }  // namespace bie

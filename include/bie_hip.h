@@ -865,6 +865,29 @@ int bie_mxfp6_linear_grad_input(const void* gy, const uint8_t* qweight, const ui
 int bie_mxfp6_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                              void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 (w6a16) mixture of experts
+ * The expert GEMM of the mxfp4 mixture-of-experts section on stacked MXFP6 weights, fp16 / bf16 activations (MXFP6ExpertsLinearCuda,
+ * MXFP6A16MoECuda; INTEGRATION.md, "MXFP6 W6A16 mixture-of-experts layer").  T, S, P, idx, x_per_pair and bias are that section's.
+ *   qweight  uint8 [E, N, 3K/4] (16-byte aligned), scales uint8 [E, N, K/32], e_col uint8 [E, N] = bie_mxfp4_col_exp on the
+ *            [E * N, K/32] view: the bytes of the mxfp6 w6a8 mixture-of-experts section, i.e. the mxfp6 (w6a16) format on the [E * N, K] view
+ *   y[p, :]  = dt( x_row(p) . W[idx[p]]^T + bias[idx[p]] ),  x_row(p) = x[p / S] (x_per_pair = 0, x is [T, K]) or x[p] (x_per_pair = 1):
+ *              products exact, the sum in fp32, one rounding to the dtype (0=f16 1=bf16)
+ *   y[p, :]  = +0 where idx[p] is outside [0, E): the index is compared before any address is formed from it
+ *   A row of y depends on its own pair only; a NaN block (scale 255) of expert e makes its column NaN for the pairs of e only.  Nothing
+ *   synchronises with the host; grids are sized from P and E; expert and row offsets are 64-bit.
+ *   K % 32 == 0, 32 <= K <= 2^20; N >= 1; 1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22; dtype fp16 or bf16.
+ * bie_mxfp6_moe_form: 0 = routed decode form (one launch, P <= 1024; a pair's row has the bits of bie_mxfp6_linear_forward's decode form
+ *   at M = 1), 1 = grouped prefill form (the routing kernel and a grouped MFMA GEMM; a pair's row has the bits of the dense prefill
+ *   form).  The plan takes the decode form for P <= 64, and for P <= 256 while P <= 2 E (measured; it came out where the mxfp4
+ *   section's rule is).  BIE_MXFP6_MOE_FORM=0/1 forces a form (0 only where P <= 1024).  Host only.
+ * bie_mxfp6_moe_forward: form -1 = bie_mxfp6_moe_form.  The prefill form needs e_col and the workspace (bie_mxfp4_moe_workspace_bytes(P, E)
+ *   bytes, 16-byte aligned; it need not be initialised); the decode form reads neither (NULL is accepted) and keeps the fp32 range of W,
+ *   while the prefill form rebiases each column by e_col (the mxfp6 (w6a16) section's range note).  Form 0 with P > 1024:
+ *   BIE_ERR_UNSUPPORTED.  Every argument is validated on the host before any device call, with the return codes of bie_mxfp4_moe_forward. */
+int bie_mxfp6_moe_form(long P, long E, long N, long K, int dtype);
+int bie_mxfp6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
