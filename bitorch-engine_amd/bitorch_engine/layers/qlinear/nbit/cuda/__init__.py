@@ -14,3 +14,4 @@ from .mxfp6_experts_a8_layer import MXFP6A8ExpertsLinearCuda, MXFP6A8ExpertsLine
 from .mxfp6_experts_layer import MXFP6ExpertsLinearCuda, MXFP6ExpertsLinearForward
 from .mxfp6_moe_layer import MXFP6MoECuda, MXFP6A16MoECuda
 from .mxfp6_layer import MXFP6LinearCuda, MXFP6LinearForward
+from .mxfp6_a6_layer import MXFP6A6LinearCuda, MXFP6A6LinearForward

@@ -7,7 +7,8 @@ KNOWN = ("q_linear_cuda", "binary_linear_cpp", "binary_linear_cuda", "binary_lin
          "binary_conv_cpp", "binary_conv2d_cutlass", "functions_cuda", "q_linear_cutlass", "q4_conv_cutlass",
          "ternary_linear_cuda", "ternary_conv2d_cuda", "ternary_a8_linear_cuda", "mxfp4_linear_cuda", "mxfp4_a4_linear_cuda",
          "mxfp4_experts_cuda", "mxfp4_experts_a4_cuda", "mxfp4_a8_linear_cuda", "mxfp4_experts_a8_cuda",
-         "mxfp6_a8_linear_cuda", "mxfp6_experts_a8_cuda", "mxfp6_linear_cuda", "mxfp6_experts_cuda")
+         "mxfp6_a8_linear_cuda", "mxfp6_experts_a8_cuda", "mxfp6_linear_cuda", "mxfp6_experts_cuda",
+         "mxfp6_a6_linear_cuda")
 
 
 class ExtensionModulePlaceholder:

@@ -2,7 +2,8 @@
 // rounding rule, code <-> fp32, a block's 24 bytes <-> its 32 codes, the FP6 operand of the block-scaled matrix instructions, and
 // mx6a8_gemm_tile on v_mfma_scale_f32_32x32x64_f8f6f4 with an FP6 A operand (cbsz 2) and an E4M3 B operand (blgp 0), and the
 // input-gradient 128 x 128 tile body (mx6_dgrad_tile: the kernels of mxfp6_grad.hip), and the weight-only (W6A16) 128 x 128 tile body
-// (mx6_gemm_tile: mx6_gemm_kernel of mxfp6.hip).  The E8M0 block scales, the block-scale rule
+// (mx6_gemm_tile: mx6_gemm_kernel of mxfp6.hip), and the W6A6 activation quantiser's unit and prefill tile body (a6_quantize_unit,
+// mx6a6_gemm_tile with two FP6 operands, cbsz 2 and blgp 2: the kernels of mxfp6_a6.hip).  The E8M0 block scales, the block-scale rule
 // (mx_block_scale: emax = 2 for E2M3 as for E2M1), the row sources and the MXFP8 activations are those of mxfp4_common.cuh /
 // mxfp4_a8_common.cuh.
 //
@@ -209,6 +210,225 @@ __device__ __forceinline__ void mx6a8_gemm_tile(const Rows& rows, const uint8_t*
     // C/D: D column (= tile row) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh: registers 4q .. 4q + 3 are four
     // consecutive n of one row -> one 8-byte store where N allows it.  A flagged row of x and a column with e_col = 255 are NaN; the bias
     // is added after that, as in mxa8_gemm_tile.
+    const bool vec = (N & 3) == 0;
+#pragma unroll
+    for (int i = 0; i < WM; i++) {
+        const int row = wy * 32 * WM + i * 32 + rl;
+        if (!rows.live(row)) continue;
+        const bool rbad = row_flag[rows.src(row)] != 0;
+        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + rows.dst(row) * N;
+#pragma unroll
+        for (int j = 0; j < WN; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int n = n0 + wx * 32 * WN + j * 32 + 8 * q + 4 * hh;
+                if (n >= N) continue;
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    v[r] = acc[j][i][4 * q + r];
+                    if (n + r < N) {
+                        if (rbad || ecol[r0 + n + r] == 255u) v[r] = a4_nan();
+                        if (bias) v[r] += dt_traits<DT>::load(bias, r0 + n + r);
+                    }
+                }
+                if (vec) {
+                    uint16_t h[4];
+                    dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
+                    dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
+                    uint2_t o;
+                    o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+                    o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+                    *reinterpret_cast<uint2_t*>(yr + n) = o;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (n + r < N) dt_traits<DT>::store(yr, n + r, v[r]);
+                }
+            }
+    }
+}
+
+// ---- the W6A6 prefill tile ------------------------------------------------------------------------------------------------------------------
+// One 8-value unit (16 bytes of x) of a block of 32 whose four units sit on the four lanes of a quad, for the MXFP6 activation quantiser
+// (mx6a6_quantize_kernel of mxfp6_a6.hip): the block maximum over the quad on the DPP network, the block's E8M0 code (mx_block_scale, the
+// weight quantiser's) and this lane's eight E2M3 codes by exactly mx6_quantize_kernel's expression, code i in bits 6 i .. 6 i + 5 of the
+// 48-bit result.  An all-zero block: scale code 0, codes 0.  `bad` collects a NaN or +-inf.  All lanes of the quad must call it together.
+template <int DT>
+__device__ __forceinline__ void a6_quantize_unit(const uint4_t& raw, int& bad, uint64_t& codes, uint32_t& scode) {
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if constexpr (DT == BIE_F16) {
+            v[2 * i] = f16_bits_to_f32(w[i] & 0xffffu);
+            v[2 * i + 1] = f16_bits_to_f32(w[i] >> 16);
+        } else {
+            v[2 * i] = bf16_bits_to_f32(w[i] & 0xffffu);
+            v[2 * i + 1] = bf16_bits_to_f32(w[i] >> 16);
+        }
+    }
+    float amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        amax = fmaxf(amax, fabsf(v[i]));
+        bad |= (__float_as_uint(v[i]) & 0x7f800000u) == 0x7f800000u;
+    }
+    amax = a4_dpp_max<0xB1>(amax);  // quad_perm [1, 0, 3, 2]
+    amax = a4_dpp_max<0x4E>(amax);  // quad_perm [2, 3, 0, 1]
+    codes = 0ull;
+    scode = 0u;
+    if (amax > 0.0f) {
+        float inv;
+        scode = mx_block_scale(amax, inv);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            codes |= (uint64_t)(mx6_round_e2m3(fminf(fabsf(v[i] * inv), 7.5f)) | ((__float_as_uint(v[i]) >> 26) & 32u)) << (6 * i);
+    }
+}
+
+// One (64 WM rows) x (64 WN columns) tile of the W6A6 product: mx6a8_gemm_tile with MXFP6 activations.  xq6 [rows, 3K/4] / xs / row_flag
+// are indexed by `rows`; columns n0 .. of the N weight rows that start at row r0 of qw / sc / ecol / bias (0, or (long)e * N for an expert
+// e).  Both operands are the same bytes: 24-byte blocks, code j in bits 6 j .. 6 j + 5, which is how the instructions read a lane's six
+// registers on EITHER side when both operands are FP6 (tools/probe/probe_mx_fp6x6.hip part (a), profiles/mxfp6_a6_probe.txt), so both
+// fragments are 24-byte copies.  4 waves as 2 x 2; per 64 k a wave reads WM x fragments and WN weight fragments (three 8-byte reads
+// each: block 2 ks + hh of the stage) with as many scale bytes and issues WM * WN v_mfma_scale_f32_32x32x64_f8f6f4 with cbsz 2 and
+// blgp 2.  The weight fragment is the A operand and the x fragment the B operand, so a lane's accumulator holds 4 consecutive columns
+// of one row of y.  LDS stage, double-buffered and filled through registers: x codes [64 WM][104], weight codes [64 WN][104] (the pitch
+// and its bank argument at A6_WPITCH: an x row has the same 96 bytes per 128-k stage and is read by the same lanes in the same way),
+// x scales [64 WM] dwords, weight scales [64 WN] dwords: 27648 bytes at WM = WN = 2, 55296 for the two buffers.  Rows of either operand
+// are read from memory in 8-byte pieces (12 per row and stage): a row's pitch is 24 K / 32 bytes, so nothing wider is aligned.  Dead
+// rows and whatever lies past N / K: zero codes under scale 2^0.  All 256 threads must call it together.
+template <int DT, int WM, int WN, class Rows>
+__device__ __forceinline__ void mx6a6_gemm_tile(const Rows& rows, const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs,
+                                                const uint8_t* __restrict__ row_flag, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, long r0, int n0,
+                                                int N, int K) {
+    constexpr int BM = 64 * WM, BN = 64 * WN, ROWS = BM + BN;
+    constexpr int XLD = BM * 12 / 256, WLD = BN * 12 / 256;  // 8-byte pieces per thread and stage: row = piece / 12
+    constexpr int WOFF = BM * A6_WPITCH, SOFF = WOFF + BN * A6_WPITCH;
+    constexpr int STAGE = SOFF + ROWS * 4;
+    static_assert(ROWS <= 256, "at most one scale dword per thread and stage");
+    static_assert(2 * STAGE <= 65536, "static LDS");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int KB = K >> 5, KT = (K + A6_BK - 1) / A6_BK;
+    const long rowb = (long)KB * MX6_BLOCK_BYTES;
+
+    // load slots: x pieces t, t + 256, ... then weight pieces (12 per row: block part / 3 of the stage, 8-byte third part % 3); thread
+    // t < ROWS also loads the scales of row t of the stage image (rows 0 .. BM - 1 = x, BM .. = weights)
+    const uint8_t* xsrc[XLD];
+    const uint8_t* wsrc[WLD];
+    bool xok[XLD], wok[WLD];
+    int xpart[XLD], xdst[XLD], wpart[WLD], wdst[WLD];
+#pragma unroll
+    for (int i = 0; i < XLD; i++) {
+        const int p = t + 256 * i, row = p / 12;
+        xpart[i] = p - row * 12;
+        xdst[i] = row * A6_WPITCH + xpart[i] * 8;
+        xok[i] = rows.live(row);
+        xsrc[i] = xq + (xok[i] ? rows.src(row) : 0L) * rowb + xpart[i] * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < WLD; i++) {
+        const int p = t + 256 * i, row = p / 12;
+        wpart[i] = p - row * 12;
+        wdst[i] = WOFF + row * A6_WPITCH + wpart[i] * 8;
+        wok[i] = n0 + row < N;
+        wsrc[i] = qw + (r0 + min(n0 + row, N - 1)) * rowb + wpart[i] * 8;
+    }
+    const bool s_thread = ROWS == 256 || t < ROWS;
+    bool sok = false;
+    const uint8_t* ssrc = xs;
+    if (s_thread) {
+        if (t < BM) {
+            sok = rows.live(t);
+            ssrc = xs + (sok ? rows.src(t) : 0L) * KB;
+        } else {
+            sok = n0 + t - BM < N;
+            ssrc = sc + (r0 + min(n0 + t - BM, N - 1)) * KB;
+        }
+    }
+    uint2_t rx[XLD], rw[WLD];
+    uint32_t rs = 0x7f7f7f7fu;
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int i = 0; i < XLD; i++) {
+            const int kb = kt * 4 + xpart[i] / 3;
+            rx[i] = (xok[i] && kb < KB) ? *reinterpret_cast<const uint2_t*>(xsrc[i] + (long)kt * A6_WROW) : uint2_t{0u, 0u};
+        }
+#pragma unroll
+        for (int i = 0; i < WLD; i++) {
+            const int kb = kt * 4 + wpart[i] / 3;
+            rw[i] = (wok[i] && kb < KB) ? *reinterpret_cast<const uint2_t*>(wsrc[i] + (long)kt * A6_WROW) : uint2_t{0u, 0u};
+        }
+        if (s_thread) {
+            rs = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int kb = kt * 4 + j;
+                const uint32_t s = (sok && kb < KB) ? (uint32_t)ssrc[kb] : 127u;
+                rs |= s << (8 * j);
+            }
+        }
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < XLD; i++) *reinterpret_cast<uint2_t*>(st + xdst[i]) = rx[i];
+#pragma unroll
+        for (int i = 0; i < WLD; i++) *reinterpret_cast<uint2_t*>(st + wdst[i]) = rw[i];
+        if (s_thread) reinterpret_cast<uint32_t*>(st + SOFF)[t] = rs;
+    };
+
+    float16_t acc[WN][WM];  // [weight row block j][x row block i]: D rows = columns n of y, D columns = rows of the tile
+#pragma unroll
+    for (int j = 0; j < WN; j++)
+#pragma unroll
+        for (int i = 0; i < WM; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[j][i][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < KT; kt++) {
+        const int buf = kt & 1;
+        if (kt + 1 < KT) load(kt + 1);
+        const unsigned char* st = lds + buf * STAGE;
+        const uint32_t* ss = reinterpret_cast<const uint32_t*>(st + SOFF);
+        uint32_t sxa[WM], swa[WN];  // the row's four scale bytes, shifted so that this lane's block of k-step ks sits in byte 2 ks
+#pragma unroll
+        for (int i = 0; i < WM; i++) sxa[i] = ss[wy * 32 * WM + i * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int j = 0; j < WN; j++) swa[j] = ss[BM + wx * 32 * WN + j * 32 + rl] >> (8 * hh);
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            mxa4_v8i fx[WM], fw[WN];
+#pragma unroll
+            for (int i = 0; i < WM; i++) {
+                const uint2_t* p = reinterpret_cast<const uint2_t*>(st + (wy * 32 * WM + i * 32 + rl) * A6_WPITCH + (ks * 2 + hh) * MX6_BLOCK_BYTES);
+                fx[i] = a6_frag(p[0], p[1], p[2]);
+            }
+#pragma unroll
+            for (int j = 0; j < WN; j++) {
+                const uint2_t* p = reinterpret_cast<const uint2_t*>(st + WOFF + (wx * 32 * WN + j * 32 + rl) * A6_WPITCH + (ks * 2 + hh) * MX6_BLOCK_BYTES);
+                fw[j] = a6_frag(p[0], p[1], p[2]);
+            }
+#pragma unroll
+            for (int j = 0; j < WN; j++)
+#pragma unroll
+                for (int i = 0; i < WM; i++)
+                    acc[j][i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[j], fx[i], acc[j][i], 2, 2, 0, (int)((swa[j] >> (16 * ks)) & 0xffu), 0,
+                                                                                (int)((sxa[i] >> (16 * ks)) & 0xffu));
+        }
+        if (kt + 1 < KT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D as in mx6a8_gemm_tile: D column (= tile row) = lane & 31, D row (= column n of y) = (r & 3) + 8 (r >> 2) + 4 hh.  A flagged row
+    // of x and a column with e_col = 255 are NaN; the bias is added after that.
     const bool vec = (N & 3) == 0;
 #pragma unroll
     for (int i = 0; i < WM; i++) {

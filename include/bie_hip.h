@@ -786,6 +786,35 @@ int bie_mxfp6_a8_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp6 w6a6
+ * MXFP6 weights (the mxfp6 w6a8 section's qweight / scales / e_col, byte for byte) x activations quantised to the same format,
+ * contracted on the block-scaled matrix instructions with two FP6 operands (MXFP6A6LinearCuda; INTEGRATION.md, "MXFP6 W6A6 linear
+ * layer").  No reference implementation; these definitions are this library's own.
+ *   xq6      uint8 [M, 3K/4] (16-byte aligned), xs uint8 [M, K/32]: x per row and block of 32 by exactly the rule of bie_mxfp6_quantize, in
+ *            the format of qweight / scales: 24-byte blocks, code j in bits 6 j .. 6 j + 5, E8M0 scales, an all-zero block = scale code
+ *            0 and 24 zero bytes.  bie_mxfp6_dequant decodes them.
+ *   row_flag uint8 [M]: 1 where row m of x holds a NaN or +-inf (the row's codes are then unspecified), else 0
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e2m3(xq6[m,k]) * e2m3(qweight[n,k])) + bias[n] ): sums in fp32 in
+ *              any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ * bie_mxfp6_quantize_act: x [M, K] (dtype 0/1, 16-byte aligned) -> xq6 (16-byte aligned), xs, row_flag.  On a finite row bit-identical to
+ *   bie_mxfp6_quantize of the same values.
+ * bie_mxfp6_a6_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP6_A6_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mxfp6_a6_workspace_bytes: the bytes bie_mxfp6_a6_linear_forward needs: xq6 [M, 3K/4] (16-byte aligned), then xs, then row_flag, the
+ *   whole rounded up to 16 (any form); 0 for a shape the layer refuses.  Host only.  bie_mxfp6_a6_gemm needs no workspace (NULL is accepted).
+ * bie_mxfp6_a6_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction: two launches.
+ *   form -1 = bie_mxfp6_a6_form.  e_col is required by both forms.
+ * bie_mxfp6_a6_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call, with the return codes of the w6a8 entries; nothing synchronises with
+ * the host. */
+int bie_mxfp6_quantize_act(const void* x, uint8_t* xq6, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream);
+int bie_mxfp6_a6_form(long M, long N, long K, int dtype);
+size_t bie_mxfp6_a6_workspace_bytes(long M, long N, long K, int form);
+int bie_mxfp6_a6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                                void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mxfp6_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                      const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp6 (w6a16)
  * MXFP6 weights (the mxfp6 w6a8 section's qweight / scales, byte for byte) against fp16 / bf16 activations: the mxfp4 section's contract
  * with E2M3 elements (MXFP6LinearCuda; INTEGRATION.md, "MXFP6 linear layer").  The semantics are defined by this library:
