@@ -545,10 +545,11 @@ int bie_ternary_conv2d_forward_mfma(const void* x, const uint8_t* wimage, const 
  * bie_ternary_a8_quantize: x [M, K] (16-byte aligned) -> q [M, ldq] int8 (16-byte aligned; ldq >= K, ldq % 16 == 0; bytes K .. ldq - 1 of
  *   each row are zeroed) and r [M] fp32.
  * bie_ternary_a8_fused_ok: 1 where the one-launch decode form is taken (small M; the bound was measured against the GEMM form).  Host only.
- * bie_ternary_a8_linear_fused: the whole layer in one launch from x (16-byte aligned).
- * bie_ternary_a8_linear_gemm: the same y on the matrix pipe from q / r of bie_ternary_a8_quantize with ldq >= K rounded up to 64.
- * raw != 0: y is int32 [M, N] = D, and alpha must be NULL (r may be NULL too).  Both linear entries are bit-identical to each other, y
- * 16-byte aligned; every argument is validated on the host before any device call. */
+ * bie_ternary_a8_linear_fused: the whole layer in one launch from x (16-byte aligned); y 4-byte aligned (it is stored element by element).
+ * bie_ternary_a8_linear_gemm: the same y on the matrix pipe from q / r of bie_ternary_a8_quantize with ldq >= K rounded up to 64; y
+ *   16-byte aligned (it is stored four elements at a time).
+ * raw != 0: y is int32 [M, N] = D, and alpha must be NULL (r may be NULL too).  Both linear entries are bit-identical to each other; r
+ * 4-byte and alpha 2-byte aligned; every argument is validated on the host before any device call. */
 int bie_ternary_a8_quantize(const void* x, int8_t* q, float* r, long M, long K, long ldq, int dtype, void* stream);
 int bie_ternary_a8_fused_ok(long M, long N, long K);
 int bie_ternary_a8_linear_fused(const void* x, const uint8_t* qweight, const void* alpha, void* y, long M, long N, long K, int dtype, int raw,
@@ -704,7 +705,8 @@ int bie_mxfp4_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* 
  * bie_mxfp4_moe_a4_forward: the whole layer from x; form -1 = bie_mxfp4_moe_a4_form.  In the decode form with K <= 32768 (a row's
  *   K/2 + K/32 bytes of codes and scale bytes, 17408 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
  *   pair's row itself, bit for bit as bie_mxfp4_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
- *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight, y, workspace 16-byte aligned.
+ *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight and y 16-byte aligned, and the workspace wherever it
+ *   is read (every form but that one launch; only there is its alignment checked).
  * bie_mxfp4_moe_a4_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq from memory and
  *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
  * e_col (bie_mxfp4_col_exp on the [E * N, K] view) is required by every form.  Every argument is validated on the host before any device
@@ -740,7 +742,8 @@ int bie_mxfp4_moe_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* r
  * bie_mxfp4_moe_a8_forward: the whole layer from x; form -1 = bie_mxfp4_moe_a8_form.  In the decode form with K <= 16384 (a row's
  *   K + K/32 bytes of codes and scale bytes, 16896 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
  *   pair's row itself, bit for bit as bie_mxfp8_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
- *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight, y, workspace 16-byte aligned.
+ *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight and y 16-byte aligned, and the workspace wherever it
+ *   is read (every form but that one launch; only there is its alignment checked).
  * bie_mxfp4_moe_a8_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq from memory and
  *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
  * e_col (bie_mxfp4_col_exp on the [E * N, K] view) is required by every form.  Every argument is validated on the host before any device
@@ -856,7 +859,8 @@ int bie_mxfp6_linear_forward(const void* x, const uint8_t* qweight, const uint8_
  * bie_mxfp6_moe_a8_forward: the whole layer from x; form -1 = bie_mxfp6_moe_a8_form.  In the decode form with K <= 16384 (a row's
  *   K + K/32 bytes of codes and scale bytes, 16896 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
  *   pair's row itself, bit for bit as bie_mxfp8_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
- *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight, y, workspace 16-byte aligned.
+ *   form is the quantise launch and the routed kernel reading xq from the workspace.  x, qweight and y 16-byte aligned, and the workspace wherever it
+ *   is read (every form but that one launch; only there is its alignment checked).
  * bie_mxfp6_moe_a8_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq from memory and
  *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
  * e_col is required by every form.  Every argument is validated on the host before any device call, with the return codes of
@@ -893,7 +897,8 @@ int bie_mxfp6_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* r
  * bie_mxfp6_moe_a6_forward: the whole layer from x; form -1 = bie_mxfp6_moe_a6_form.  In the decode form with K <= 16384 (a row's
  *   3K/4 + K/32 bytes of codes and scale bytes, 12800 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
  *   pair's row itself, bit for bit as bie_mxfp6_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
- *   form is the quantise launch and the routed kernel reading xq6 from the workspace.  x, qweight, y, workspace 16-byte aligned.
+ *   form is the quantise launch and the routed kernel reading xq6 from the workspace.  x, qweight and y 16-byte aligned, and the workspace wherever it
+ *   is read (every form but that one launch; only there is its alignment checked).
  * bie_mxfp6_moe_a6_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq6 from memory and
  *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
  * e_col is required by every form.  Every argument is validated on the host before any device call, with the return codes of
