@@ -193,6 +193,15 @@ int mxfp6_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* ro
 int mxfp6_a6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st);
 
+// mxfp4_a6.hip
+int mxfp4_a6_form(long M, long N, long K, int dtype);
+bool mxfp4_a6_decode_ok(long M);
+size_t mxfp4_a6_workspace_bytes(long M, long K);
+int mxfp4_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                         const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st);
+int mxfp4_a6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
+                            long N, long K, int dtype, int form, hipStream_t st);
+
 // mxfp6.hip
 int mxfp6_form(long M, long N, long K, int dtype);
 bool mxfp6_decode_ok(long M);
@@ -1295,6 +1304,48 @@ int bie_mxfp6_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_
     BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
                 "bie_mxfp6_a6_gemm: xq6, qweight and y must be 16-byte aligned, bias 2-byte aligned");
     return mxfp6_a6_gemm_launch(xq6, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+}
+
+// ---- MXFP4 W4A6 (MXFP4 weights, MXFP6 activations: bie_mxfp6_quantize_act's).  Everything is checked here, before any device call; the
+// shape limits are W4A4's (check_mx, check_mxa4), the return codes the W4A8 entries'.
+static int check_mx4a6_form(const char* what, long M, long N, long K, int dtype, int* form) {
+    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
+    if (*form < 0) *form = mxfp4_a6_form(M, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || mxfp4_a6_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
+    return BIE_OK;
+}
+
+int bie_mx4a6_form(long M, long N, long K, int dtype) { return mxfp4_a6_form(M, N, K, dtype); }
+
+size_t bie_mx4a6_workspace_bytes(long M, long N, long K, int form) {
+    (void)N; (void)form;
+    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
+    return mxfp4_a6_workspace_bytes(M, K);
+}
+
+int bie_mx4a6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                             void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mxa4("bie_mx4a6_linear_forward", M, N, K, dtype);
+    if (rc) return rc;
+    rc = check_mx4a6_form("bie_mx4a6_linear_forward", M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mx4a6_linear_forward: NULL tensor pointer");
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mx4a6_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
+    return mxfp4_a6_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+}
+
+int bie_mx4a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                   const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
+    (void)workspace;  // neither form needs one beyond the quantised activations it is given
+    int rc = check_mxa4("bie_mx4a6_gemm", M, N, K, dtype);
+    if (rc) return rc;
+    rc = check_mx4a6_form("bie_mx4a6_gemm", M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq6 && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mx4a6_gemm: NULL tensor pointer");
+    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mx4a6_gemm: xq6, qweight and y must be 16-byte aligned, bias 2-byte aligned");
+    return mxfp4_a6_gemm_launch(xq6, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
 }
 
 // ---- MXFP6 weight-only (W6A16).  Everything is checked here, before any device call; the shape limits are the MXFP4 layer's.

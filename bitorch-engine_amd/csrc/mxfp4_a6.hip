@@ -1,0 +1,213 @@
+// MXFP4 W4A6 linear layer for gfx950: the MXFP4 weights of mxfp4.hip (qweight / scales, unchanged) against activations quantised to
+// MXFP6 (OCP E2M3 elements, E8M0 block scales) on the fly by the W6A6 layer's quantiser, contracted on the block-scaled matrix
+// instructions with an FP4 A operand and an FP6 B operand: the FP4 matrix rate (an E4M3 operand costs twice the cycles) at the
+// activation accuracy of MXFP8 (include/bie_hip.h, INTEGRATION.md "MXFP4 W4A6 linear layer").
+//
+//   xq6 uint8 [M, 3K/4], xs uint8 [M, K/32], row_flag uint8 [M]: the outputs of mx6a6_quantize_kernel (mxfp6_a6.hip), byte for byte:
+//       e = clamp(floor(log2 amax) - 2, -127, 127), code = e2m3(clamp(|v * 2^-e|, 7.5)) round to nearest, ties to the even code;
+//       24 bytes per block, code j in bits 6 j .. 6 j + 5; row_flag[m] = 1 where row m of x holds a NaN or +-inf
+//   y[m, n] = dt( sum_b 2^(xs[m, b] + scales[n, b] - 254) * (sum_{k in b} e2m3(xq6) * e2m1(qweight)) + bias[n] )
+//   y[m, :] = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255 (a weight block with scale code 255)
+//
+// How the instructions read this mixed pair was pinned on the card by tools/probe/probe_mx_fp4x6.hip (profiles/mxfp4_a6_probe.txt),
+// A = FP4 (cbsz 4, four VGPRs), B = FP6 E2M3 (blgp 2, six VGPRs), both shapes:
+//   (a)  either operand is one block of 32 per lane: lane group g (l >> 5 in v_mfma_scale_f32_32x32x64_f8f6f4, l >> 4 in
+//        v_mfma_scale_f32_16x16x128_f8f6f4) holds k = 32 g .. 32 g + 31; the FP4 element j sits in bits 4 j .. 4 j + 3 of the four
+//        registers, the FP6 element j in bits 6 j .. 6 j + 5 of the six, little-endian: the layouts of qweight and of xq6, so the weight
+//        fragment is a 16-byte copy and the x fragment a 24-byte copy (unlike the E4M3 B operand of W4A8, which is split in two halves)
+//   (b)  the scale byte of lane group g applies to block g of the instruction's K on either operand (byte select 0)
+//   (c)  under one scale an instruction is exact (the products lie on a 2^-4 grid); where its blocks differ in scale it is inexact
+//        against float64, the figure in tests/mxfp4_a6_ref.py (PROBE_ULPS)
+// The one-hot selector test of tests/test_mxfp4_a6_gpu.py holds the element maps in the suite.
+//
+// There is no quantise kernel here: mxfp6_a6_quantize_launch is called as it stands.  Decode form (mx4a6_decode_kernel, M <= 64):
+// mxa8_decode_kernel's structure; a lane's weight fragment is one non-temporal 16-byte load and its x fragment its block's 24 bytes in
+// three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx4a6_gemm_tile of mxfp4_a6_common.cuh.
+#include "mxfp4_a6_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+int mxfp6_a6_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);  // mxfp6_a6.hip
+
+// ---- decode form ------------------------------------------------------------------------------------------------------------------------
+// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
+// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15 and block l >> 4 of the step on both sides: 16 bytes of codes and a scale
+// byte of the weights, 24 bytes of codes and a scale byte of every 16-row group of x.  Blocks past K and rows past M enter as zero codes
+// under scale 2^0 (code 127).  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one row of y.
+template <int DT, int G>
+__global__ __launch_bounds__(256) void mx4a6_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                           const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                           const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
+    __shared__ mxa4_v4f red[3][G][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const long xrowb = (long)KB * MX6_BLOCK_BYTES;
+    const int n0 = blockIdx.x * 16;
+    const long nl = min(n0 + r16, N - 1);
+    const uint8_t* wrow = qw + nl * (K >> 1);
+    const uint8_t* srow = sc + nl * KB;
+    mxa4_v4f acc[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t w = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow) + kc);
+        int sw = __builtin_nontemporal_load(srow + kc);
+        uint2_t a0[G], a1[G], a2[G];
+        int sa[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const long m = min(g * 16 + r16, M - 1);
+            const uint2_t* xp = reinterpret_cast<const uint2_t*>(xq + m * xrowb + (long)kc * MX6_BLOCK_BYTES);
+            a0[g] = xp[0];
+            a1[g] = xp[1];
+            a2[g] = xp[2];
+            sa[g] = xs[m * KB + kc];
+        }
+        if (!kin) {
+            w = uint4_t{0u, 0u, 0u, 0u};
+            sw = 127;
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (!kin || g * 16 + r16 >= M) {
+                a0[g] = a1[g] = a2[g] = uint2_t{0u, 0u};
+                sa[g] = 127;
+            }
+        }
+        const mxa4_v8i fw = a4_frag(w);
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, a6_frag(a0[g], a1[g], a2[g]), acc[g], 4, 2, 0, sw, 0, sa[g]);
+    }
+    if (wave) {
+#pragma unroll
+        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
+    }
+    __syncthreads();
+    if (wave) return;
+    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y
+    const int n = n0 + 4 * kq;
+    if (n >= N) return;
+    const bool vec = (N & 3) == 0;
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const int m = g * 16 + r16;
+        if (m >= M) continue;
+        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
+        const bool rbad = row_flag[m] != 0;
+        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
+            if (n + r < N) {
+                if (rbad || ecol[n + r] == 255u) v[r] = a4_nan();
+                if (bias) v[r] += dt_traits<DT>::load(bias, n + r);
+            }
+        }
+        if (vec) {
+            uint16_t h[4];
+            dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
+            dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
+            uint2_t o;
+            o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+            o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+            *reinterpret_cast<uint2_t*>(yr + n) = o;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (n + r < N) dt_traits<DT>::store(yr, n + r, v[r]);
+        }
+    }
+}
+
+// ---- prefill form -----------------------------------------------------------------------------------------------------------------------
+// A workgroup per (64 WM) x (64 WN) tile (mx4a6_gemm_tile), the tiles walked in pipe_tile's order.
+template <int DT, int WM, int WN>
+__global__ __launch_bounds__(256) void mx4a6_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                         const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
+                                                         const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
+    int tile_m, tile_n;
+    pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
+    mx4a6_gemm_tile<DT, WM, WN>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The decode form serves M <= A46_DECODE_ROWS (instances of 16, 32 and 64 rows); larger M takes the prefill form.
+// The plan's bound is measured (tools/mxfp4_a6_bench.py, profiles/mxfp4_a6_bench.jsonl, the "sweep" rows: both forms forced at M = 8 .. 64,
+// alternated, the median of three passes, the quantise launch included, fp16 and bf16 alike within 2 %): the decode form was ahead at
+// every M <= 32 on 4096 x 4096, 4096 -> 11008 and 11008 -> 4096 (0.27 - 0.74 x the prefill form's time), level at M = 48 on 4096 -> 11008
+// (40.8 against 41.3 us) and ahead there on the other two (0.51 / 0.39), and at M = 64 ahead on two of the three shapes (22.6 / 41.3 us
+// against 41.2 / 92.4) and 13 % behind on 4096 -> 11008 (47.7 against 42.1 us).  The bound stays at 64: what the prefill form would
+// lose there on the other two shapes (82 % and 124 %) outweighs that, as for W4A8 and W6A6.
+constexpr int A46_DECODE_ROWS = 64;
+constexpr int A46_PLAN_ROWS = 64;
+
+bool mxfp4_a6_decode_ok(long M) { return M >= 1 && M <= A46_DECODE_ROWS; }
+
+int mxfp4_a6_form(long M, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_A6_FORM", -1);
+    if (f == 0 && M <= A46_DECODE_ROWS) return 0;
+    if (f == 1) return 1;
+    return M <= A46_PLAN_ROWS ? 0 : 1;
+}
+
+// Workspace of bie_mx4a6_linear_forward: xq6 [M, 3K/4] (16-byte aligned), xs [M, K/32], row_flag [M]: the W6A6 layer's layout
+static size_t a46_xs_offset(long M, long K) { return (size_t)(M * (K / 32) * MX6_BLOCK_BYTES); }
+static size_t a46_flag_offset(long M, long K) { return a46_xs_offset(M, K) + (size_t)(M * (K / 32)); }
+size_t mxfp4_a6_workspace_bytes(long M, long K) { return (a46_flag_offset(M, K) + (size_t)M + 15) / 16 * 16; }
+
+template <int DT, int WM, int WN>
+static void a46_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const int tn = cdiv(N, 64 * WN);
+    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
+    hipLaunchKernelGGL((mx4a6_gemm_kernel<DT, WM, WN>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
+}
+
+template <int DT>
+static void a46_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                               const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    // 128 x 128 tiles where they give every CU of the card (256) at least two workgroups, else 64 x 64 tiles, as in the W4A8 launcher
+    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) a46_gemm_launch_t<DT, 2, 2>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+    else a46_gemm_launch_t<DT, 1, 1>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
+}
+
+template <int DT>
+static void a46_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                                 const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+    const dim3 grid((unsigned)cdiv(N, 16));
+    if (M <= 16) hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else if (M <= 32) hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+    else hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
+}
+
+int mxfp4_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                         const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
+    if (form == 0) {
+        if (dtype == BIE_F16) a46_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        else a46_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+        return check_launch("mx4a6_decode_kernel");
+    }
+    if (dtype == BIE_F16) a46_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    else a46_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
+    return check_launch("mx4a6_gemm_kernel");
+}
+
+int mxfp4_a6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
+                            long N, long K, int dtype, int form, hipStream_t st) {
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a46_xs_offset(M, K);
+    uint8_t* rf = xq + a46_flag_offset(M, K);
+    const int rc = mxfp6_a6_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_a6_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+}
+
+}  // namespace bie

@@ -818,6 +818,33 @@ int bie_mxfp6_a6_linear_forward(const void* x, const uint8_t* qweight, const uin
 int bie_mxfp6_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 w4a6
+ * MXFP4 weights x activations quantised to MXFP6 (E2M3 elements, E8M0 block scales) on the fly, contracted on the block-scaled matrix
+ * instructions with an FP4 and an FP6 operand, which run at the FP4 rate (MXFP4A6LinearCuda; INTEGRATION.md, "MXFP4 W4A6 linear layer").
+ * qweight / scales / e_col are those of the mxfp4 section above, unchanged; the activations are those of the mxfp6 w6a6 section, byte
+ * for byte.  No reference implementation; these definitions are this library's own.
+ *   xq6      uint8 [M, 3K/4] (16-byte aligned), xs uint8 [M, K/32], row_flag uint8 [M]: the outputs of bie_mxfp6_quantize_act (24-byte
+ *            blocks, code j in bits 6 j .. 6 j + 5, E8M0 scales; row_flag[m] = 1 where row m of x holds a NaN or +-inf)
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e2m3(xq6[m,k]) * e2m1(qweight[n,k])) + bias[n] ): sums in fp32 in
+ *              any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ * There is no quantise entry of its own: bie_mxfp6_quantize_act is the quantiser.
+ * bie_mx4a6_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP4_A6_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mx4a6_workspace_bytes: the bytes bie_mx4a6_linear_forward needs: xq6 [M, 3K/4] (16-byte aligned), then xs, then row_flag, the
+ *   whole rounded up to 16 (any form; the layout of bie_mxfp6_a6_workspace_bytes); 0 for a shape the layer refuses.  Host only.
+ *   bie_mx4a6_gemm needs no workspace (NULL is accepted).
+ * bie_mx4a6_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction: two launches.
+ *   form -1 = bie_mx4a6_form.  e_col (bie_mxfp4_col_exp) is required by both forms.
+ * bie_mx4a6_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call, with the return codes of the w4a8 entries; nothing synchronises with
+ * the host. */
+int bie_mx4a6_form(long M, long N, long K, int dtype);
+size_t bie_mx4a6_workspace_bytes(long M, long N, long K, int form);
+int bie_mx4a6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                             void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mx4a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                   const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp6 (w6a16)
  * MXFP6 weights (the mxfp6 w6a8 section's qweight / scales, byte for byte) against fp16 / bf16 activations: the mxfp4 section's contract
  * with E2M3 elements (MXFP6LinearCuda; INTEGRATION.md, "MXFP6 linear layer").  The semantics are defined by this library:
