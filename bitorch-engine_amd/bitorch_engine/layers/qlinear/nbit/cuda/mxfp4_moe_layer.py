@@ -16,13 +16,16 @@ quantise x and a to MXFP4 per row and block of 32 and contract on the block-scal
 router, the top-k softmax, the SwiGLU and the combine are the same ops.
 activations="mxfp8" ("MXFP4 W4A8 mixture-of-experts layer"): gate_up and down are MXFP4A8ExpertsLinearCuda, which
 quantise x and a to MXFP8 (E4M3 elements, E8M0 block scales) per row and block of 32 and contract on the same instructions with an FP4
-and an E4M3 operand (csrc/mxfp4_moe_a8.hip); everything else is the same ops.  The default "dtype" is the block above, untouched."""
+and an E4M3 operand (csrc/mxfp4_moe_a8.hip); everything else is the same ops.  The default "dtype" is the block above, untouched.
+MXFP4A6MoECuda ("MXFP4 W4A6 mixture-of-experts layer") is the same block with MXFP6 (E2M3) activations; it is a class
+of its own, not a value of `activations`."""
 import torch
 from torch import nn
 
 from .mxfp4_experts_layer import MXFP4ExpertsLinearCuda
 from .mxfp4_experts_a4_layer import MXFP4A4ExpertsLinearCuda
 from .mxfp4_experts_a8_layer import MXFP4A8ExpertsLinearCuda
+from .mxfp4_experts_a6_layer import MXFP4A6ExpertsLinearCuda
 
 
 def swiglu(h: torch.Tensor, limit: float, alpha: float) -> torch.Tensor:
@@ -106,3 +109,21 @@ class MXFP4MoECuda(nn.Module):
         a = swiglu(h, self.swiglu_limit, self.swiglu_alpha)
         o = self.down(a, idx)
         return combine(w, o).reshape(*lead, self.hidden)
+
+
+class MXFP4A6MoECuda(MXFP4MoECuda):
+    """The same block on MXFP4 expert weights with MXFP6 activations ("MXFP4 W4A6 mixture-of-experts layer"): gate_up and
+    down are MXFP4A6ExpertsLinearCuda, which quantise x and a to E2M3 elements with E8M0 block scales per row and block of 32 and contract
+    them with the E2M1 weight codes on the block-scaled matrix instructions with an FP4 and an FP6 operand (csrc/mxfp4_moe_a6.hip).
+    Within a block a value below 1/64 of the block's power-of-two maximum becomes zero; that matters most for the SwiGLU output a that
+    feeds down.  The parameters and buffers are MXFP4MoECuda's, so the blocks load each other's state_dict, and load_gpt_oss_experts is
+    inherited: the checkpoint's expert tensors are taken as they are."""
+
+    def __init__(self, hidden: int, intermediate: int, num_experts: int, top_k: int, bias: bool = True, swiglu_limit: float = 7.0,
+                 swiglu_alpha: float = 1.702, device: torch.device = None, dtype: torch.dtype = torch.bfloat16) -> None:
+        super().__init__(hidden, intermediate, num_experts, top_k, bias=bias, swiglu_limit=swiglu_limit, swiglu_alpha=swiglu_alpha, device=device,
+                         dtype=dtype, activations="dtype")
+        self.activations = "mxfp6"
+
+    def _experts_class(self, activations: str):
+        return MXFP4A6ExpertsLinearCuda

@@ -231,6 +231,17 @@ int mxfp6_moe_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t
 int mxfp6_moe_a6_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                                 void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
 
+// mxfp4_moe_a6.hip
+int mxfp4_moe_a6_form(long P, long E, long N, long K, int dtype);
+bool mxfp4_moe_a6_decode_ok(long P);
+bool mxfp4_moe_a6_one_launch_ok(long K);
+size_t mxfp4_moe_a6_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form);
+int mxfp4_moe_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st);
+int mxfp4_moe_a6_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
+
 // mxfp4_moe.hip
 int mxfp4_moe_form(long P, long E, long N, long K, int dtype);
 bool mxfp4_moe_decode_ok(long P);
@@ -1637,6 +1648,57 @@ int bie_mxfp6_moe_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* 
                     (form == 0 || !misaligned(workspace, 16)),
                 BIE_ERR_INVALID_ARG, "%s: xq6, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
     return mxfp6_moe_a6_gemm_launch(xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
+                                    as_stream(stream));
+}
+
+// ---- MXFP4 W4A6 mixture of experts.  Everything is checked here, before any device call; the checks are the W6A6 expert entries'
+// (check_mx_moe_act, and the column tiles counted at 64 columns, the narrower of this layer's two tile widths).
+int bie_mx4a6_moe_form(long P, long E, long N, long K, int dtype) { return mxfp4_moe_a6_form(P, E, N, K, dtype); }
+
+size_t bie_mx4a6_moe_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
+    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
+    if (form == 0 && !mxfp4_moe_a6_decode_ok(T * S)) return 0;
+    return mxfp4_moe_a6_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
+}
+
+static int check_mx4a6_moe(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
+    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
+    if (rc) return rc;
+    const long P = T * S;
+    BIE_REQUIRE((P / 128 + E + 1) * ((N + 63) / 64) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: P * N = %ld beyond the layer's range (the grid of 128 x 64 tiles)",
+                fn, P * N);
+    if (*form < 0) *form = mxfp4_moe_a6_form(P, E, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || mxfp4_moe_a6_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
+    return BIE_OK;
+}
+
+int bie_mx4a6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    const char* fn = "bie_mx4a6_moe_forward";
+    int rc = check_mx4a6_moe(fn, T, S, E, N, K, x_per_pair, dtype, &form);
+    if (rc) return rc;
+    const bool need_ws = form == 1 || !mxfp4_moe_a6_one_launch_ok(K);
+    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
+                    (!need_ws || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
+    return mxfp4_moe_a6_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+}
+
+int bie_mx4a6_moe_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                       const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                       int dtype, int form, void* stream) {
+    const char* fn = "bie_mx4a6_moe_gemm";
+    int rc = check_mx4a6_moe(fn, T, S, E, N, K, x_per_pair, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq6 && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
+    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
+                    (form == 0 || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: xq6, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
+    return mxfp4_moe_a6_gemm_launch(xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
                                     as_stream(stream));
 }
 

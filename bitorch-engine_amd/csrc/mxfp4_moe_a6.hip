@@ -1,0 +1,302 @@
+// MXFP4 W4A6 expert GEMM for gfx950: stacked MXFP4 expert weights (E2M1 elements, E8M0 block scales; the format of mxfp4_moe.hip per
+// expert) against activations quantised to MXFP6 (E2M3 elements, E8M0 block scales) on the fly (mxfp6_a6.hip's xq6 / xs / row_flag),
+// contracted on the block-scaled matrix instructions with an FP4 and an FP6 operand, at the FP4 matrix rate (include/bie_hip.h,
+// INTEGRATION.md "MXFP4 W4A6 mixture-of-experts layer").  It is mxfp6_moe_a6.hip with the weight side of mxfp4_a6.hip.  No reference
+// implementation exists.
+//
+//   T tokens, S slots per token, P = T * S pairs; pair p = t * S + s uses expert idx[p]; row(p) = p / S (x_per_pair = 0) or p
+//   qweight uint8 [E, N, K/2]: per row K/32 blocks of 16 bytes, code j of a block in bits 4 j .. 4 j + 3 (the dense layer's bit order)
+//   scales uint8 [E, N, K/32]; e_col uint8 [E, N] = bie_mxfp4_col_exp on the [E * N, K/32] view
+//   xq6 uint8 [R, 3K/4] / xs uint8 [R, K/32] / row_flag uint8 [R]: the stored rows of x (R = T or P) by the rule of
+//   mx6a6_quantize_kernel (mxfp6_a6.hip): 24-byte blocks, code j in bits 6 j .. 6 j + 5
+//   y[p, n] = dt( sum_b 2^(xs[row(p), b] + scales[e, n, b] - 254) * (sum_{k in b} e2m3(xq6) * e2m1(qweight)) + bias[e, n] ),  e = idx[p]
+//   y[p, :] = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255; y[p, :] = +0 where idx[p] is outside [0, E), whatever
+//   the row's flag: the index is compared before any address is formed from it
+//
+// A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
+// row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
+//
+// Routed decode form (mx4m6_decode_kernel, P <= 1024): mx6m6_decode_kernel's structure (mxfp6_moe_a6.hip): a workgroup per pair and strip
+// of 16 C16 columns of its expert, K split over the 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4 with an FP4 A and an FP6
+// B operand (cbsz 4, blgp 2, byte select 0; profiles/mxfp4_a6_probe.txt): the weight fragment is A (one non-temporal 16-byte load at
+// row * K/2 + block * 16, and its scale byte), the x fragment B: the lanes with (lane & 15) == 0 hold the 24 bytes of block lane >> 4 of
+// the step of the pair's row (column 0 of B) with its scale byte; all other columns, and blocks past K on either side, are zero codes
+// under scale code 127.  The four partial sums meet in LDS and are summed as ((w0 + w1) + w2) + w3, the order of mx4a6_decode_kernel
+// (mxfp4_a6.hip): a pair's row has the bits of the dense W4A6 decode form.
+// FUSED (one launch, K <= MX4M6_ONE_K): the workgroup quantises x_row(p) into LDS itself, with the code of mx6m6_decode_kernel (the x
+// side is identical: a6_quantize_unit and the quad-neighbour exchange of mx6a6_quantize_kernel, the bits of bie_mxfp6_quantize_act; 3K/4
+// code bytes, K/32 scale bytes, the non-finite flag through the barrier) and reads neither xq6 nor a workspace.  Not FUSED: it reads
+// xq6 / xs / row_flag from memory.
+// Grouped prefill form: mx6a6_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
+// mx4m6_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx4a6_gemm_tile (mxfp4_a6_common.cuh) at 128 x 128 or 128 x 64.  A row tile
+// belongs to one expert, gathers the xq6 / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the
+// segment enter as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the
+// skipped bin run no K loop and store zeros.
+#include "mxfp4_a6_common.cuh"
+
+#pragma clang fp contract(off)
+
+namespace bie {
+
+// mxfp6_a6.hip, mxfp4_moe.hip
+int mxfp6_a6_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
+size_t mxfp4_moe_workspace_bytes(long P, long E);
+long mxfp4_moe_max_tiles(long P, long E);
+int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
+
+// ---- routed decode form -------------------------------------------------------------------------------------------------------------------
+// The largest K of the one-launch form, the sibling expert kernels' bound.  A row's image in LDS is 3K/4 code bytes and K/32 scale
+// bytes: 12800 bytes at the bound (the W4A8 expert kernel's image is K + K/32 = 16896).
+constexpr int MX4M6_ONE_K = 16384;
+constexpr int MX4M6_IMG_CODES = MX4M6_ONE_K / 32 * MX6_BLOCK_BYTES;  // 12288
+constexpr int MX4M6_DECODE_PAIRS = 1024;                             // the grid's second dimension
+static_assert(MX4M6_IMG_CODES + MX4M6_ONE_K / 32 == 12800, "the row image of the one-launch form");
+
+// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
+// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step's weights (16 bytes and
+// a scale byte); the lanes with (l & 15) == 0 hold the same block of the pair's row of x, 24 bytes and a scale byte.  xin is x (FUSED)
+// or xq6.
+template <int DT, int C16, bool FUSED>
+__global__ __launch_bounds__(256) void mx4m6_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                           const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                           const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                           int N, int K, int x_per_pair) {
+    constexpr int C = 16 * C16;
+    __shared__ float red[4][C];
+    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MX4M6_IMG_CODES + MX4M6_ONE_K / 32 : 16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r16 = lane & 15, kq = lane >> 4;
+    const int p = blockIdx.y, n0 = blockIdx.x * C;
+    const int e = idx[p];
+    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
+        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
+        return;
+    }
+    const int KB = K >> 5, KS = (KB + 3) >> 2;
+    const long xrowb = (long)KB * MX6_BLOCK_BYTES, wrowb = K >> 1;
+    const long xrow = x_per_pair ? p : p / S;
+    const unsigned char* xqr;  // the row's code bytes: the LDS image or xq6
+    const unsigned char* xsr;  // its scale bytes
+    int flagged;
+    if constexpr (FUSED) {
+        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
+        const int U = K >> 3;  // a multiple of 4 and the stride is 256: whole quads are in or out, so the quad's exchanges are complete
+        int bad = 0;
+        for (int u = t; u < U; u += 256) {
+            uint64_t c;
+            uint32_t scode;
+            a6_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
+            // the right neighbour's codes: quad_perm [1, 2, 3, 0] (mx6a6_quantize_kernel)
+            const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)c, 0x39, 0xf, 0xf, false);
+            const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(c >> 32), 0x39, 0xf, 0xf, false);
+            const uint64_t nb = (uint64_t)nlo | ((uint64_t)nhi << 32);
+            const int q = u & 3;
+            if (q < 3) {
+                const uint64_t word = (c >> (16 * q)) | (nb << (48 - 16 * q));
+                *reinterpret_cast<uint2_t*>(img + (u >> 2) * MX6_BLOCK_BYTES + q * 8) = uint2_t{(uint32_t)word, (uint32_t)(word >> 32)};
+            }
+            if (q == 0) img[KB * MX6_BLOCK_BYTES + (u >> 2)] = (unsigned char)scode;
+        }
+        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
+        xqr = img;
+        xsr = img + KB * MX6_BLOCK_BYTES;
+    } else {
+        xqr = reinterpret_cast<const unsigned char*>(xin) + xrow * xrowb;
+        xsr = xs + xrow * KB;
+        flagged = row_flag[xrow];
+    }
+    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
+    const uint8_t* wrow[C16];
+    const uint8_t* srow[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) {
+        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
+        wrow[c] = qw + n * wrowb;
+        srow[c] = sc + n * KB;
+    }
+    mxa4_v4f acc[C16];
+#pragma unroll
+    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
+    for (int s = wave; s < KS; s += 4) {
+        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
+        const bool kin = kb < KB;
+        uint4_t w[C16];
+        int sw[C16];
+#pragma unroll
+        for (int c = 0; c < C16; c++) {
+            w[c] = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow[c]) + kc);
+            sw[c] = __builtin_nontemporal_load(srow[c] + kc);
+        }
+        // this lane's x fragment: block kb of the pair's row in column 0, zero codes under scale 2^0 everywhere else
+        uint2_t a0 = uint2_t{0u, 0u}, a1 = uint2_t{0u, 0u}, a2 = uint2_t{0u, 0u};
+        int sa = 127;
+        if (r16 == 0 && kin) {
+            const uint2_t* xp = reinterpret_cast<const uint2_t*>(xqr + (long)kb * MX6_BLOCK_BYTES);
+            a0 = xp[0];
+            a1 = xp[1];
+            a2 = xp[2];
+            sa = xsr[kb];
+        }
+        if (!kin) {
+#pragma unroll
+            for (int c = 0; c < C16; c++) {
+                w[c] = uint4_t{0u, 0u, 0u, 0u};
+                sw[c] = 127;
+            }
+        }
+        const mxa4_v8i fx = a6_frag(a0, a1, a2);
+#pragma unroll
+        for (int c = 0; c < C16; c++) acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(w[c]), fx, acc[c], 4, 2, 0, sw[c], 0, sa);
+    }
+    // C/D: D column (= row of the x operand) = lane & 15, D row (= column n of the strip) = 4 (lane >> 4) + r: the pair's row is
+    // registers 0 .. 3 of lanes 0, 16, 32, 48
+    if (r16 == 0) {
+#pragma unroll
+        for (int c = 0; c < C16; c++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) red[wave][c * 16 + 4 * kq + r] = acc[c][r];
+    }
+    __syncthreads();
+    if (t < C) {
+        const int n = n0 + t;
+        if (n < N) {
+            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
+            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
+            dt_traits<DT>::store(y, (long)p * N + n, v);
+        }
+    }
+}
+
+// ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
+// The routing's row tile fixes WM = 2.  A stage of mx4a6_gemm_tile at WM = WN = 2 is 13312 bytes of x codes, 10240 of weight codes and
+// 1024 of scale dwords: 49152 for the two buffers, 49664 beside the pair list (the W4A8 grouped tile stages 59392 bytes, the W6A6 one
+// 55296).  WN = 1 (128 x 64): 2 (13312 + 5120 + 768) + 512 = 38912.
+constexpr int MX4M6_WM = 2;
+static_assert(64 * MX4M6_WM == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
+static_assert(2 * (64 * MX4M6_WM * A6_WPITCH + 128 * A4_PITCH + (64 * MX4M6_WM + 128) * 4) + MXM_BM * 4 == 49664, "static LDS of the 128 x 128 instance");
+static_assert(2 * (64 * MX4M6_WM * A6_WPITCH + 64 * A4_PITCH + (64 * MX4M6_WM + 64) * 4) + MXM_BM * 4 == 38912, "static LDS of the 128 x 64 instance");
+static_assert(49664 <= 65536, "static LDS");
+
+// A workgroup per (row tile of the table, column tile): mx4a6_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+template <int DT, int WN>
+__global__ __launch_bounds__(256) void mx4m6_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
+                                                         const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
+                                                         const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
+                                                         int N, int K, int x_per_pair, int max_tiles) {
+    __shared__ int prow[MXM_BM];
+    int e, n0;
+    if (!mxm_tile_begin<DT, 64 * WN>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
+    mx4a6_gemm_tile<DT, MX4M6_WM, WN>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+}
+
+// ---- plan and launchers -------------------------------------------------------------------------------------------------------------------
+// The routed decode form exists for P <= MX4M6_DECODE_PAIRS.  The plan started from the W4A8 expert layer's constants (decode for
+// P <= 32, and up to P = 128 while P <= E; mxfp4_moe_a8.hip) and was then measured (tools/mxfp4_moe_a6_bench.py,
+// profiles/mxfp4_moe_a6_bench.jsonl, the `sweep` rows: both gpt-oss-20b projections at E = 32 and E = 128, fp16 and bf16, both forms
+// forced at P = 1, 2, 4, ..., 1024, graph time, routings and weight stacks rotated, the grouped form on 128 x 128 tiles; fp16 and bf16
+// agree within 2 % but for 9 of the 88 pairs of figures, up to 12 %: no verdict below turns on that).  The decode form grows linearly
+// in P (8.7 / 15.8 / 47 / 88 / 170 / 337 us at P = 1 / 4 / 16 / 32 / 64 / 128 on 2880 -> 5760); the grouped form costs 42 us at P = 1
+// and then grows with the number of experts that hold a pair.  At E = 32 the decode form led at every P <= 32 (P = 32: 88 against
+// 140 - 147 us at 5760, 47 against 81 - 82 at 2880); P = 64 was split (170 against 168 at 5760: level; 88 - 89 against 103 at 2880:
+// decode ahead) and the grouped form led from P = 128 on (337 against 170, 172 - 173 against 112 - 113).  At E = 128 the decode form
+// led through P = 128 (P = 64: 169 against 270 - 272, 89 - 90 against 160 - 162; P = 128: 332 against 428 - 433, 173 - 174 against
+// 225 - 226) and the grouped form from P = 256 on (657 - 658 against 542 - 556, 340 against 313 - 316).  Those are the W4A8 layer's
+// crossovers, so the constants stay: they take the faster form on 86 of the 88 rows; the other two are 2880 -> 2880 at E = 32, P = 64
+// (the grouped form taken, 103 us against the decode form's 88 - 89), where 2880 -> 5760 is level.  A first bound of 64 would take
+// those two and lose 1 % on the level pair, but it would also hold for E < 32, which was not measured and where the grouped form has
+// fewer experts to visit.  E between 32 and 128 and beyond 128, and P between the powers of two, were not measured.  The strip width
+// of the decode form is the W4A8 layer's measured 16 columns; other widths were not measured here.
+constexpr int MX4M6_PLAN_PAIRS = 32, MX4M6_PLAN_PAIRS_SPARSE = 128;
+constexpr int MX4M6_STRIP = 1;  // C16 of the decode form
+// The column tile of the grouped form, WN = 2 (128 x 128) or WN = 1 (128 x 64); BIE_MXFP4_MOE_A6_WN = 1 / 2 selects the instance and a
+// row's bits do not depend on it.  Measured (the `tile` rows: T = 64, 256, 4096 at S = 4, both projections, E = 32 and E = 128, fp16 and
+// bf16, the two widths captured as two graphs and alternated for 9 rounds, spread at most 0.9 %): 128 x 128 was ahead on 20 of the 24 rows
+// (0.78 - 0.83 x the 128 x 64 time at T = 4096 on every shape; 0.89 - 0.95 x at T = 64 and 256 on 2880 -> 5760 and on 2880 -> 2880 with
+// E = 128) and behind on 4 (2880 -> 2880, E = 32, T = 64 and 256: 1.10 - 1.14 x, 113 / 133 against 99 / 120 us, the rows on which the
+// W6A6 expert layer's wide tile is behind as well).  The majority ships: 128 x 128.  A width chosen per call from max_tiles and N was
+// not tried.
+constexpr int MX4M6_WN = 2;
+
+bool mxfp4_moe_a6_decode_ok(long P) { return P >= 1 && P <= MX4M6_DECODE_PAIRS; }
+bool mxfp4_moe_a6_one_launch_ok(long K) { return K <= MX4M6_ONE_K; }
+
+int mxfp4_moe_a6_form(long P, long E, long N, long K, int dtype) {
+    (void)N; (void)K; (void)dtype;
+    const int f = BIE_KNOB("BIE_MXFP4_MOE_A6_FORM", -1);
+    if (f == 0 && P <= MX4M6_DECODE_PAIRS) return 0;
+    if (f == 1) return 1;
+    return (P <= MX4M6_PLAN_PAIRS || (P <= MX4M6_PLAN_PAIRS_SPARSE && P <= E)) ? 0 : 1;
+}
+
+// Workspace of bie_mx4a6_moe_forward, the W6A6 expert layer's layout: xq6 [R, 3K/4], xs [R, K/32], row_flag [R] for the R stored rows
+// of x (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip; every region 16-byte aligned.
+static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
+static long a46m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
+static size_t a46m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)(K / 32) * MX6_BLOCK_BYTES); }
+static size_t a46m_flag_offset(long R, long K) { return a46m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
+static size_t a46m_route_offset(long R, long K) { return a46m_flag_offset(R, K) + al16((size_t)R); }
+
+size_t mxfp4_moe_a6_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    return a46m_route_offset(a46m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+}
+
+template <int DT, bool FUSED>
+static int a46m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                              const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
+    const dim3 grid((unsigned)cdivl(N, 16 * MX4M6_STRIP), (unsigned)P);
+    hipLaunchKernelGGL((mx4m6_decode_kernel<DT, MX4M6_STRIP, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N,
+                       (int)K, xpp);
+    return check_launch("mx4m6_decode_kernel");
+}
+
+template <int DT, int WN>
+static void a46m_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const int32_t* ws, const uint8_t* qw, const uint8_t* sc,
+                               const uint8_t* ecol, const void* bias, void* y, long S, long E, long N, long K, int xpp, int max_tiles, hipStream_t st) {
+    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * WN)));
+    hipLaunchKernelGGL((mx4m6_gemm_kernel<DT, WN>), grid, dim3(256), 0, st, xq, xs, rf, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, xpp,
+                       max_tiles);
+}
+
+// The contraction from quantised activations.  form 0: the routed kernel reading xq6 from memory (no workspace); form 1: routing into the
+// workspace (the routing region alone), then the grouped GEMM.
+int mxfp4_moe_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
+                             const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                             int dtype, int form, hipStream_t st) {
+    const long P = T * S;
+    if (form == 0) {
+        if (dtype == BIE_F16) return a46m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a46m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
+    if (rc) return rc;
+    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
+    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
+    const bool wide = BIE_KNOB("BIE_MXFP4_MOE_A6_WN", MX4M6_WN) >= 2;
+    if (dtype == BIE_F16) {
+        if (wide) a46m_gemm_launch_t<BIE_F16, 2>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
+        else a46m_gemm_launch_t<BIE_F16, 1>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
+    } else {
+        if (wide) a46m_gemm_launch_t<BIE_BF16, 2>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
+        else a46m_gemm_launch_t<BIE_BF16, 1>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
+    }
+    return check_launch("mx4m6_gemm_kernel");
+}
+
+// The whole layer from x.  form 0 with K <= MX4M6_ONE_K: one launch, the workspace is not touched.
+int mxfp4_moe_a6_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                                void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
+    const long P = T * S, R = a46m_rows(T, S, x_per_pair);
+    if (form == 0 && K <= MX4M6_ONE_K) {
+        if (dtype == BIE_F16) return a46m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+        return a46m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
+    }
+    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
+    uint8_t* xs = xq + a46m_xs_offset(R, K);
+    uint8_t* rf = xq + a46m_flag_offset(R, K);
+    const int rc = mxfp6_a6_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
+    if (rc) return rc;
+    return mxfp4_moe_a6_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a46m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+}
+
+}  // namespace bie

@@ -938,6 +938,45 @@ int bie_mxfp6_moe_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* 
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp4 w4a6 mixture of experts
+ * The expert GEMM of the mxfp4 w4a8 mixture-of-experts section with the activations of the mxfp6 w6a6 section: stacked MXFP4 weights
+ * against rows of x quantised to MXFP6 (E2M3), contracted on the block-scaled matrix instructions with an FP4 and an FP6 operand, at
+ * the FP4 rate (MXFP4A6ExpertsLinearCuda, MXFP4A6MoECuda; INTEGRATION.md, "MXFP4 W4A6 mixture-of-experts layer").  T, S, P, idx,
+ * x_per_pair, qweight [E, N, K/2], scales, e_col and bias are the w4a8 expert section's, unchanged; xq6, xs and row_flag are
+ * bie_mxfp6_quantize_act's of the R stored rows of x (R = T, or P with x_per_pair).  row(p) = p / S (x_per_pair = 0) or p.
+ *   y[p, n]  = dt( sum_b 2^(xs[row(p),b] + scales[e,n,b] - 254) * (sum_{k in b} e2m3(xq6[row(p),k]) * e2m1(qweight[e,n,k])) + bias[e,n] ),
+ *              e = idx[p]: sums in fp32 in any order, one rounding to the dtype (0=f16 1=bf16): the mxfp4 w4a6 section's contract per pair
+ *   y[p, :]  = NaN where row_flag[row(p)]; y[p, n] = NaN where e_col[e, n] == 255 (a NaN block of expert e reaches the pairs of e only)
+ *   y[p, :]  = +0 where idx[p] is outside [0, E): no bias and no NaN, even for a flagged row; the index is compared before any address
+ *              is formed from it
+ *   A row of y depends on its own pair only; in the decode form it has the bits of bie_mx4a6_gemm's decode form on that expert, in the
+ *   prefill form those of its prefill form.  Nothing synchronises with the host; grids are sized from P and E; expert and row offsets
+ *   are 64-bit.  K % 32 == 0, 32 <= K <= 2^20; N >= 1; 1 <= E <= 1024; 1 <= S <= 32; 1 <= P <= 2^22; dtype fp16 or bf16.
+ * bie_mx4a6_moe_form: 0 = routed decode form (P <= 1024), 1 = grouped prefill form (quantise launch, routing kernel, grouped
+ *   block-scaled GEMM on 128 x 128 tiles; BIE_MXFP4_MOE_A6_WN=1 takes 128 x 64 tiles, with the same bits).  The plan takes the decode
+ *   form for P <= 32, and for P <= 128 while P <= E (measured; the w4a8 expert section's constants).  BIE_MXFP4_MOE_A6_FORM=0/1 forces a form (0 only
+ *   where P <= 1024).  Host only.
+ * bie_mx4a6_moe_workspace_bytes: what bie_mx4a6_moe_forward needs, every region 16-byte aligned: xq6 [R, 3K/4], xs [R, K/32] and
+ *   row_flag [R], then (form 1) the routing region of bie_mxfp4_moe_workspace_bytes(P, E): the layout of
+ *   bie_mxfp6_moe_a6_workspace_bytes.  form -1 gives the form-1 size, which serves either form.  0 for a refused shape (form 0 with
+ *   P > 1024 included).  Host only.
+ * bie_mx4a6_moe_forward: the whole layer from x; form -1 = bie_mx4a6_moe_form.  In the decode form with K <= 16384 (a row's
+ *   3K/4 + K/32 bytes of codes and scale bytes, 12800 at the bound, are held in LDS) this is ONE launch: every workgroup quantises its
+ *   pair's row itself, bit for bit as bie_mxfp6_quantize_act, and the workspace is not read (NULL is accepted).  Beyond that K the decode
+ *   form is the quantise launch and the routed kernel reading xq6 from the workspace.  x, qweight and y 16-byte aligned, and the
+ *   workspace wherever it is read (every form but that one launch; only there is its alignment checked).
+ * bie_mx4a6_moe_gemm: the contraction from already-quantised activations.  Form 0 is the routed kernel reading xq6 from memory and
+ *   takes no workspace (NULL); form 1 needs the routing region alone, bie_mxfp4_moe_workspace_bytes(P, E) bytes, 16-byte aligned.
+ * e_col is required by every form.  Every argument is validated on the host before any device call, with the return codes of
+ * bie_mxfp4_moe_a8_forward. */
+int bie_mx4a6_moe_form(long P, long E, long N, long K, int dtype);
+size_t bie_mx4a6_moe_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form);
+int bie_mx4a6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
+int bie_mx4a6_moe_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                       const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                       int dtype, int form, void* stream);
+
 /* ------------------------------------------------------------------------------------------ mxfp6 input gradient
  * gx = gy . W straight from the packed weights of the mxfp6 w6a8 and mxfp6 w6a8 mixture-of-experts sections, for the backward of their
  * layers ("MXFP6 input gradient"): the mxfp4 input gradient's contract with E2M3 elements.  qweight / scales are those
