@@ -176,6 +176,12 @@ SIGNATURES = {
     "bie_mx4a6_moe_gemm": (_i, [_vp] * 10 + [_l] * 5 + [_i, _i, _i, _vp]),
     "bie_mxfp6_moe_form": (_i, [_l] * 4 + [_i]),
     "bie_mxfp6_moe_forward": (_i, [_vp] * 8 + [_l] * 5 + [_i, _i, _i, _vp]),
+    "bie_mx8_quantize": (_i, [_vp] * 3 + [_l] * 2 + [_i, _vp]),
+    "bie_mx8_dequant": (_i, [_vp] * 3 + [_l] * 2 + [_i, _vp]),
+    "bie_mx8a8_form": (_i, [_l] * 3 + [_i]),
+    "bie_mx8a8_workspace_bytes": (_sz, [_l] * 3 + [_i]),
+    "bie_mx8a8_linear_forward": (_i, [_vp] * 7 + [_l] * 3 + [_i, _i, _vp]),
+    "bie_mx8a8_gemm": (_i, [_vp] * 9 + [_l] * 3 + [_i, _i, _vp]),
 }
 
 
@@ -191,7 +197,7 @@ _HOST_ONLY = ("bie_version", "bie_last_error", "bie_mbwq_rows", "bie_mbwq_exl2_t
               "bie_test_forge_dependency", "bie_test_mpq_forward_plan", "bie_test_mpq_gemm_plan", "bie_mpq_list_launches", "bie_mpq_list_form", "bie_mpq_prefill_form", "bie_mpq_rows_form", "bie_mpq_grouped_max_rows", "bie_mpq_list_destroy", "bie_mbwq_exl2_list_destroy",
               "bie_ternary_conv2d_form", "bie_ternary_a8_fused_ok", "bie_mxfp4_form", "bie_mxfp4_a4_form", "bie_mxfp4_a8_form", "bie_mxfp4_moe_form", "bie_mxfp4_moe_a4_form",
               "bie_mxfp4_moe_a8_form", "bie_mxfp6_a8_form", "bie_mxfp6_a6_form", "bie_mxfp6_moe_a8_form", "bie_mxfp6_form", "bie_mxfp6_moe_form",
-              "bie_mxfp6_moe_a6_form", "bie_mx4a6_form", "bie_mx4a6_moe_form")
+              "bie_mxfp6_moe_a6_form", "bie_mx4a6_form", "bie_mx4a6_moe_form", "bie_mx8a8_form")
 
 
 class ListEntry(ctypes.Structure):

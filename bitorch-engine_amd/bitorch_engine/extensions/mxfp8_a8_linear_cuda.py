@@ -1,0 +1,101 @@
+"""MXFP8 (OCP microscaling FP8, e4m3fn elements) weights x activations quantised to MXFP8 on the fly (csrc/mxfp8_a8.hip), contracted on the
+block-scaled matrix instructions with two E4M3 operands.  The format and the arithmetic are this library's own (include/bie_hip.h,
+INTEGRATION.md "MXFP8 W8A8 linear layer"):
+
+  qweight uint8 [N, K]: row-major OCP e4m3fn bytes            scales uint8 [N, K/32]  (E8M0: 2^(s - 127), 255 = NaN)
+  W[n, k] = e4m3(qweight[n, k]) * 2^(scales[n, k // 32] - 127)
+  xq uint8 [M, K], xs uint8 [M, K/32], row_flag uint8 [M]: the MXFP8 activations of mxfp4_a8_linear_cuda, unchanged
+  y[m, n] = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e4m3(xq) * e4m3(qweight)) + bias[n] ),  NaN for a flagged row
+
+quantize / dequant convert between a float weight and the (qweight, scales) pair; dequant decodes (xq, xs) as well, the bytes being the
+same format.  col_exp is the MXFP4 one (the scale bytes are the same), quantize_act and dequant_act are the W4A8 ones; gemm contracts
+already-quantised activations, forward does both.  There is no packed-weight input gradient for MXFP8.  Nothing here synchronises with
+the host, so every entry can be captured in a graph."""
+import torch
+
+from bitorch_engine import _hip
+from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, col_exp  # noqa: F401
+from bitorch_engine.extensions.mxfp4_a8_linear_cuda import _act_shape, _bias, dequant_act, quantize_act  # noqa: F401
+
+
+def _shape(qweight: torch.Tensor, scales: torch.Tensor):
+    if qweight.dtype != torch.uint8 or qweight.dim() != 2 or scales.dtype != torch.uint8 or scales.dim() != 2:
+        raise RuntimeError("mxfp8: qweight must be uint8 [N, K] and scales uint8 [N, K/32]")
+    N, KB = scales.shape
+    if KB == 0 or tuple(qweight.shape) != (N, 32 * KB):
+        raise RuntimeError(f"mxfp8: qweight {tuple(qweight.shape)} does not match scales {tuple(scales.shape)} (32 bytes per block of 32)")
+    return N, 32 * KB
+
+
+def quantize(weight: torch.Tensor):
+    """float weight [N, K] (fp32 / fp16 / bf16) -> (qweight uint8 [N, K], scales uint8 [N, K/32]) by the OCP MX rule with E4M3 elements:
+    quantize_act's rule per block, plus scale code 255 and zero bytes for a block that holds a NaN or +-inf."""
+    _hip.need_gpu(weight)
+    N, K = weight.shape
+    w = _aligned(weight.detach())
+    qweight = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    _hip.check(_hip.lib().bie_mx8_quantize(_hip.ptr(w), _hip.ptr(qweight), _hip.ptr(scales), N, K, _hip.dt(w), _hip.stream()), "bie_mx8_quantize")
+    return qweight, scales
+
+
+def dequant(qweight: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """W [N, K] in dtype: computed exactly in fp32, rounded once (fp16 overflows to inf beyond 65504)."""
+    _hip.need_gpu(qweight, scales)
+    N, K = _shape(qweight, scales)
+    w = torch.empty((N, K), dtype=dtype, device=qweight.device)
+    qweight, scales = _aligned(qweight), scales.contiguous()
+    _hip.check(_hip.lib().bie_mx8_dequant(_hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(w), N, K, _hip.dt(w), _hip.stream()), "bie_mx8_dequant")
+    return w
+
+
+def form(M: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
+    """0 = decode form, 1 = prefill form (bie_mx8a8_form)."""
+    return int(_hip.lib().bie_mx8a8_form(M, N, K, _hip._DT[dtype]))
+
+
+def forward(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor = None, e_col: torch.Tensor = None,
+            form: int = -1) -> torch.Tensor:
+    """x [M, K] (fp16 / bf16) -> y [M, N] in x's dtype: quantise x, then the contraction.  form -1 = the plan.  e_col (col_exp(scales)) is
+    computed here when it is not given."""
+    _hip.need_gpu(x, qweight, scales, bias, e_col)
+    if x.dtype not in _X_DT:
+        raise RuntimeError(f"mxfp8 a8 linear: dtype {x.dtype} is not supported (fp16 / bf16)")
+    N, K = _shape(qweight, scales)
+    if x.dim() != 2 or x.shape[1] != K:
+        raise RuntimeError(f"mxfp8 a8 linear: x {tuple(x.shape)} does not match K={K}")
+    M = x.shape[0]
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    if M == 0:
+        return y
+    L = _hip.lib()
+    if e_col is None:
+        e_col = col_exp(scales)
+    ws = torch.empty(int(L.bie_mx8a8_workspace_bytes(M, N, K, int(form))), dtype=torch.uint8, device=x.device)
+    bias = _bias(bias, x.dtype)
+    x, qweight, scales = _aligned(x), _aligned(qweight), scales.contiguous()  # held until the launches are queued
+    _hip.check(L.bie_mx8a8_linear_forward(_hip.ptr(x), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y), _hip.ptr(ws),
+                                          M, N, K, _hip.dt(x), int(form), _hip.stream()), "bie_mx8a8_linear_forward")
+    return y
+
+
+def gemm(xq: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor = None,
+         e_col: torch.Tensor = None, dtype: torch.dtype = torch.float16, form: int = -1) -> torch.Tensor:
+    """The contraction from already-quantised activations (xq uint8 [M, K], xs uint8 [M, K/32], row_flag uint8 [M]) -> y [M, N] in dtype."""
+    _hip.need_gpu(xq, xs, row_flag, qweight, scales, bias, e_col)
+    if dtype not in _X_DT:
+        raise RuntimeError(f"mxfp8 a8 gemm: dtype {dtype} is not supported (fp16 / bf16)")
+    N, K = _shape(qweight, scales)
+    M = xq.shape[0]
+    if _act_shape(xq, xs) != (M, K) or row_flag.dtype != torch.uint8 or tuple(row_flag.shape) != (M,):
+        raise RuntimeError(f"mxfp8 a8 gemm: xq {tuple(xq.shape)} / xs {tuple(xs.shape)} / row_flag {tuple(row_flag.shape)} do not match K={K}")
+    y = torch.empty((M, N), dtype=dtype, device=xq.device)
+    if M == 0:
+        return y
+    if e_col is None:
+        e_col = col_exp(scales)
+    bias = _bias(bias, dtype)
+    xq, xs, row_flag, qweight, scales = _aligned(xq), xs.contiguous(), row_flag.contiguous(), _aligned(qweight), scales.contiguous()
+    _hip.check(_hip.lib().bie_mx8a8_gemm(_hip.ptr(xq), _hip.ptr(xs), _hip.ptr(row_flag), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col),
+                                         _hip.ptr(bias), _hip.ptr(y), None, M, N, K, _hip._DT[dtype], int(form), _hip.stream()), "bie_mx8a8_gemm")
+    return y

@@ -8,7 +8,8 @@ KNOWN = ("q_linear_cuda", "binary_linear_cpp", "binary_linear_cuda", "binary_lin
          "ternary_linear_cuda", "ternary_conv2d_cuda", "ternary_a8_linear_cuda", "mxfp4_linear_cuda", "mxfp4_a4_linear_cuda",
          "mxfp4_experts_cuda", "mxfp4_experts_a4_cuda", "mxfp4_a8_linear_cuda", "mxfp4_experts_a8_cuda",
          "mxfp6_a8_linear_cuda", "mxfp6_experts_a8_cuda", "mxfp6_linear_cuda", "mxfp6_experts_cuda",
-         "mxfp6_a6_linear_cuda", "mxfp6_experts_a6_cuda", "mxfp4_a6_linear_cuda", "mxfp4_experts_a6_cuda")
+         "mxfp6_a6_linear_cuda", "mxfp6_experts_a6_cuda", "mxfp4_a6_linear_cuda", "mxfp4_experts_a6_cuda",
+         "mxfp8_a8_linear_cuda")
 
 
 class ExtensionModulePlaceholder:

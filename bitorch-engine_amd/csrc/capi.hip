@@ -172,6 +172,16 @@ int mxfp4_moe_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t
 int mxfp4_moe_a8_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                                 void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
 
+// mxfp8_a8.hip
+int mxfp8_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st);
+int mxfp8_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, long K, int dtype, hipStream_t st);
+int mxfp8_a8_form(long M, long N, long K, int dtype);
+bool mxfp8_a8_decode_ok(long M);
+int mxfp8_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                         const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st);
+int mxfp8_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
+                            long N, long K, int dtype, int form, hipStream_t st);
+
 // mxfp6_a8.hip
 int mxfp6_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st);
 int mxfp6_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, long K, int dtype, hipStream_t st);
@@ -1357,6 +1367,66 @@ int bie_mx4a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_fla
     BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
                 "bie_mx4a6_gemm: xq6, qweight and y must be 16-byte aligned, bias 2-byte aligned");
     return mxfp4_a6_gemm_launch(xq6, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+}
+
+// ---- MXFP8 W8A8 (MXFP8 weights, MXFP8 activations: bie_mxfp8_quantize_act's).  Everything is checked here, before any device call; the
+// shape limits are W4A4's (check_mx, check_mxa4), the return codes the W4A8 entries'.
+static int check_mx8a8_form(const char* what, long M, long N, long K, int dtype, int* form) {
+    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
+    if (*form < 0) *form = mxfp8_a8_form(M, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || mxfp8_a8_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
+    return BIE_OK;
+}
+
+int bie_mx8_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream) {
+    int rc = check_mx("bie_mx8_quantize", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_mx8_quantize: dtype %d (0=f16, 1=bf16, 2=f32)", dtype);
+    BIE_REQUIRE(w && qweight && scales, BIE_ERR_INVALID_ARG, "bie_mx8_quantize: NULL pointer");
+    BIE_REQUIRE(!misaligned(w, 4) && !misaligned(qweight, 16), BIE_ERR_INVALID_ARG, "bie_mx8_quantize: w must be 4-byte aligned, qweight 16-byte aligned");
+    return mxfp8_quantize_launch(w, qweight, scales, N, K, dtype, as_stream(stream));
+}
+
+int bie_mx8_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long N, long K, int dtype, void* stream) {
+    int rc = check_mx("bie_mx8_dequant", N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype >= 0 && dtype <= 2, BIE_ERR_UNSUPPORTED, "bie_mx8_dequant: dtype %d (0=f16, 1=bf16, 2=f32)", dtype);
+    BIE_REQUIRE(w && qweight && scales, BIE_ERR_INVALID_ARG, "bie_mx8_dequant: NULL pointer");
+    BIE_REQUIRE(!misaligned(w, 4) && !misaligned(qweight, 16), BIE_ERR_INVALID_ARG, "bie_mx8_dequant: w must be 4-byte aligned, qweight 16-byte aligned");
+    return mxfp8_dequant_launch(qweight, scales, w, N, K, dtype, as_stream(stream));
+}
+
+int bie_mx8a8_form(long M, long N, long K, int dtype) { return mxfp8_a8_form(M, N, K, dtype); }
+
+size_t bie_mx8a8_workspace_bytes(long M, long N, long K, int form) {
+    (void)N; (void)form;
+    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
+    return mxfp4_a8_workspace_bytes(M, K);
+}
+
+int bie_mx8a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                             void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mxa4("bie_mx8a8_linear_forward", M, N, K, dtype);
+    if (rc) return rc;
+    rc = check_mx8a8_form("bie_mx8a8_linear_forward", M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mx8a8_linear_forward: NULL tensor pointer");
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mx8a8_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
+    return mxfp8_a8_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+}
+
+int bie_mx8a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                   const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
+    (void)workspace;  // neither form needs one beyond the quantised activations it is given
+    int rc = check_mxa4("bie_mx8a8_gemm", M, N, K, dtype);
+    if (rc) return rc;
+    rc = check_mx8a8_form("bie_mx8a8_gemm", M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mx8a8_gemm: NULL tensor pointer");
+    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "bie_mx8a8_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
+    return mxfp8_a8_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
 }
 
 // ---- MXFP6 weight-only (W6A16).  Everything is checked here, before any device call; the shape limits are the MXFP4 layer's.

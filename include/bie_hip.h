@@ -1025,6 +1025,43 @@ int bie_mxfp6_moe_form(long P, long E, long N, long K, int dtype);
 int bie_mxfp6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                           void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp8 w8a8
+ * MXFP8 weights (OCP e4m3fn elements, E8M0 block scales: the element format most MX toolchains write) x activations quantised to MXFP8
+ * on the fly, contracted on the block-scaled matrix instructions with two E4M3 operands, which run at half the FP4 / FP6 rate
+ * (MXFP8A8LinearCuda; INTEGRATION.md, "MXFP8 W8A8 linear layer").  The activations are those of the mxfp4 w4a8 section, byte for byte.
+ * No reference implementation; these definitions are this library's own.
+ *   qweight  uint8 [N, K] (16-byte aligned), row-major OCP e4m3fn bytes; scales uint8 [N, K/32], E8M0, code 255 = a NaN block;
+ *            e_col uint8 [N] = bie_mxfp4_col_exp(scales).  W[n, k] = e4m3(qweight[n, k]) * 2^(scales[n, k/32] - 127)
+ *   xq       uint8 [M, K] (16-byte aligned), xs uint8 [M, K/32], row_flag uint8 [M]: the outputs of bie_mxfp8_quantize_act
+ *   y[m, n]  = dt( sum_b 2^(xs[m,b] + scales[n,b] - 254) * (sum_{k in b} e4m3(xq[m,k]) * e4m3(qweight[n,k])) + bias[n] ): sums in fp32 in
+ *              any order, one rounding to the dtype (0=f16 1=bf16)
+ *   y[m, :]  = NaN where row_flag[m]; y[:, n] = NaN where e_col[n] == 255.  K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.
+ *   A NaN code (0x7F / 0xFF) inside qweight makes y[:, n] NaN for its row n in every row of y and leaves the other columns alone (the
+ *   instruction's behaviour, tools/probe/probe_mx_fp8x8.hip part (d)); bie_mx8_quantize never writes one.  Nothing outside y is written.
+ * There is no activation quantiser of its own: bie_mxfp8_quantize_act is the quantiser.
+ * bie_mx8_quantize: w [N, K] (dtype 0=f16 1=bf16 2=f32, 4-byte aligned) -> qweight, scales by bie_mxfp8_quantize_act's rule per block of
+ *   32: e = clamp(floor(log2 amax) - 8, -127, 127), code = e4m3fn(clamp(v * 2^-e, +-448)) round to nearest even, the sign kept.  An
+ *   all-zero block: scale 0, zero bytes.  A block holding a NaN or +-inf: scale code 255, zero bytes.  Never a NaN code; idempotent on
+ *   the dequantised weights; on finite fp16 / bf16 rows the bytes of bie_mxfp8_quantize_act.
+ * bie_mx8_dequant: qweight, scales -> w [N, K] (dtype 0/1/2, 4-byte aligned), exact in fp32 and rounded once; it decodes xq / xs too.
+ * bie_mx8a8_form: 0 = decode form (M <= 64), 1 = prefill form.  BIE_MXFP8_A8_FORM=0/1 forces one (0 only where M <= 64).  Host only.
+ * bie_mx8a8_workspace_bytes: the bytes bie_mx8a8_linear_forward needs: xq [M, K] (16-byte aligned), then xs, then row_flag, the whole
+ *   rounded up to 16 (any form; the layout and value of bie_mxfp4_a8_workspace_bytes); 0 for a shape the layer refuses.  Host only.
+ *   bie_mx8a8_gemm needs no workspace (NULL is accepted).
+ * bie_mx8a8_linear_forward: the whole layer from x: quantise into the workspace (16-byte aligned), then the contraction: two launches.
+ *   form -1 = bie_mx8a8_form.  e_col (bie_mxfp4_col_exp) is required by both forms.
+ * bie_mx8a8_gemm: the contraction from already-quantised activations.
+ * Every argument is validated on the host before any device call, with the return codes of the w4a8 entries; nothing synchronises with
+ * the host or allocates. */
+int bie_mx8_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream);
+int bie_mx8_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long N, long K, int dtype, void* stream);
+int bie_mx8a8_form(long M, long N, long K, int dtype);
+size_t bie_mx8a8_workspace_bytes(long M, long N, long K, int form);
+int bie_mx8a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
+                             void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+int bie_mx8a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                   const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
