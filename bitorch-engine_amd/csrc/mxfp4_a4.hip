@@ -17,7 +17,7 @@
 // Decode form (mxa4_decode_kernel, M <= 64): a workgroup per 16 output columns, K split over its 4 waves; every wave loads its B
 // fragments straight from qweight (non-temporal, 16 bytes per lane) and the x fragments from xq (cache-resident), one
 // 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS.
-// Prefill form (mxa4_gemm_kernel): mxa4_gemm_tile of mxfp4_a4_common.cuh, a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2,
+// Prefill form (mxa4_gemm_kernel): mx_scaled_gemm_tile (FP4 x FP4) of mx_scaled_tile.cuh, a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2,
 // packed codes and scale bytes staged through registers into double-buffered LDS (128 k per stage), on the rows m0 .. of xq / xs.
 #include "mxfp4_a4_common.cuh"
 
@@ -121,14 +121,14 @@ __global__ __launch_bounds__(256) void mxa4_decode_kernel(const uint8_t* __restr
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------
-// A workgroup per (64 WM) x (64 WN) tile (mxa4_gemm_tile), the tiles walked in pipe_tile's order.
+// A workgroup per (64 WM) x (64 WN) tile (mx_scaled_gemm_tile), the tiles walked in pipe_tile's order.
 template <int DT, int WM, int WN>
 __global__ __launch_bounds__(256) void mxa4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                         const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                         const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
     int tile_m, tile_n;
     pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
-    mxa4_gemm_tile<DT, WM, WN>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
+    mx_scaled_gemm_tile<DT, WM, WN, mx_op_fp4, mx_op_fp4>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

@@ -22,8 +22,8 @@
 //
 // There is no quantise kernel here: mxfp6_a6_quantize_launch is called as it stands.  Decode form (mx4a6_decode_kernel, M <= 64):
 // mxa8_decode_kernel's structure; a lane's weight fragment is one non-temporal 16-byte load and its x fragment its block's 24 bytes in
-// three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx4a6_gemm_tile of mxfp4_a6_common.cuh.
-#include "mxfp4_a6_common.cuh"
+// three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx_scaled_gemm_tile (FP4 x FP6) of mx_scaled_tile.cuh.
+#include "mxfp6_common.cuh"
 
 #pragma clang fp contract(off)
 
@@ -90,10 +90,9 @@ __global__ __launch_bounds__(256) void mx4a6_decode_kernel(const uint8_t* __rest
     }
     __syncthreads();
     if (wave) return;
-    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y
+    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y (mx_store4)
     const int n = n0 + 4 * kq;
     if (n >= N) return;
-    const bool vec = (N & 3) == 0;
 #pragma unroll
     for (int g = 0; g < G; g++) {
         const int m = g * 16 + r16;
@@ -103,38 +102,20 @@ __global__ __launch_bounds__(256) void mx4a6_decode_kernel(const uint8_t* __rest
         uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
-            if (n + r < N) {
-                if (rbad || ecol[n + r] == 255u) v[r] = a4_nan();
-                if (bias) v[r] += dt_traits<DT>::load(bias, n + r);
-            }
-        }
-        if (vec) {
-            uint16_t h[4];
-            dt_traits<DT>::store(h, 0, v[0]); dt_traits<DT>::store(h, 1, v[1]);
-            dt_traits<DT>::store(h, 2, v[2]); dt_traits<DT>::store(h, 3, v[3]);
-            uint2_t o;
-            o.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-            o.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-            *reinterpret_cast<uint2_t*>(yr + n) = o;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (n + r < N) dt_traits<DT>::store(yr, n + r, v[r]);
-        }
+        for (int r = 0; r < 4; r++) v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
+        mx_store4<DT>(v, rbad, ecol, bias, n, yr, n, N);
     }
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------
-// A workgroup per (64 WM) x (64 WN) tile (mx4a6_gemm_tile), the tiles walked in pipe_tile's order.
+// A workgroup per (64 WM) x (64 WN) tile (mx_scaled_gemm_tile), the tiles walked in pipe_tile's order.
 template <int DT, int WM, int WN>
 __global__ __launch_bounds__(256) void mx4a6_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                          const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                          const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K, int tiles_n) {
     int tile_m, tile_n;
     pipe_tile(blockIdx.x, gridDim.x, tiles_n, BIE_PIPE_GM, tile_m, tile_n);
-    mx4a6_gemm_tile<DT, WM, WN>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
+    mx_scaled_gemm_tile<DT, WM, WN, mx_op_fp4, mx_op_fp6>(mx_rows_dense{tile_m * 64 * WM, M}, xq, xs, row_flag, qw, sc, ecol, bias, y, 0L, tile_n * 64 * WN, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@
 // workgroup quantises x_row(p) into LDS itself (a4_quantize_unit, the bits of mxa4_quantize_kernel; codes, scale bytes, and the
 // non-finite flag through the barrier) and reads neither xq nor a workspace.  Not FUSED: it reads xq / xs / row_flag from memory.
 // Grouped prefill form: mxa4_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
-// mxma4_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mxa4_gemm_tile (mxfp4_a4_common.cuh) at 128 x 128, the tile of the W4A4 linear
+// mxma4_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx_scaled_gemm_tile (mx_scaled_tile.cuh; FP4 x FP4) at 128 x 128, the tile of the W4A4 linear
 // layer's prefill form.  A row tile belongs to one expert, gathers the xq / xs rows of its pairs through the pair list (whole 16-byte
 // pieces of codes, whole scale bytes) and reads weights from (long)e * N; rows past the segment enter as zero codes under scale code
 // 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no K loop and store zeros.
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void mxma4_decode_kernel(const void* __restric
 constexpr int MXMA4_W = 2;  // WM = WN of the tile: 128 x 128
 static_assert(64 * MXMA4_W == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
 
-// A workgroup per (row tile of the table, column tile): mxa4_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+// A workgroup per (row tile of the table, column tile): mx_scaled_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
 template <int DT>
 __global__ __launch_bounds__(256) void mxma4_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                          const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void mxma4_gemm_kernel(const uint8_t* __restri
     __shared__ int prow[MXM_BM];
     int e, n0;
     if (!mxm_tile_begin<DT, 64 * MXMA4_W>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
-    mxa4_gemm_tile<DT, MXMA4_W, MXMA4_W>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+    mx_scaled_gemm_tile<DT, MXMA4_W, MXMA4_W, mx_op_fp4, mx_op_fp4>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

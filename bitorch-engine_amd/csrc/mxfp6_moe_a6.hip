@@ -26,7 +26,7 @@
 // exchange of mx6a6_quantize_kernel: the bits of bie_mxfp6_quantize_act; 3K/4 code bytes, K/32 scale bytes, the non-finite flag through
 // the barrier) and reads neither xq6 nor a workspace.  Not FUSED: it reads xq6 / xs / row_flag from memory.
 // Grouped prefill form: mx6a6_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
-// mx6m6_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx6a6_gemm_tile (mxfp6_common.cuh) at 128 x 128 or 128 x 64.  A row tile
+// mx6m6_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx_scaled_gemm_tile (mx_scaled_tile.cuh; FP6 x FP6) at 128 x 128 or 128 x 64.  A row tile
 // belongs to one expert, gathers the xq6 / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the
 // segment enter as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the
 // skipped bin run no K loop and store zeros.
@@ -171,13 +171,13 @@ __global__ __launch_bounds__(256) void mx6m6_decode_kernel(const void* __restric
 
 // ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------
 // The routing's row tile fixes WM = 2.  Unlike the W6A8 grouped GEMM (mxfp6_moe_a8.hip, MX6M_WM) the 128 x 128 instance fits: a stage of
-// mx6a6_gemm_tile is 27648 bytes at WM = WN = 2, 55296 for the two buffers, 55808 beside the pair list.  WN = 1 (128 x 64) takes 41984.
+// mx_scaled_gemm_tile is 27648 bytes at WM = WN = 2, 55296 for the two buffers, 55808 beside the pair list.  WN = 1 (128 x 64) takes 41984.
 constexpr int MX6M6_WM = 2;
 static_assert(64 * MX6M6_WM == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
-static_assert(2 * ((64 * MX6M6_WM + 128) * A6_WPITCH + (64 * MX6M6_WM + 128) * 4) + MXM_BM * 4 == 55808, "static LDS of the 128 x 128 instance");
+static_assert(2 * ((64 * MX6M6_WM + 128) * mx_op_fp6::pitch(128) + (64 * MX6M6_WM + 128) * 4) + MXM_BM * 4 == 55808, "static LDS of the 128 x 128 instance");
 static_assert(55808 <= 65536, "static LDS");
 
-// A workgroup per (row tile of the table, column tile): mx6a6_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+// A workgroup per (row tile of the table, column tile): mx_scaled_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
 template <int DT, int WN>
 __global__ __launch_bounds__(256) void mx6m6_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                          const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void mx6m6_gemm_kernel(const uint8_t* __restri
     __shared__ int prow[MXM_BM];
     int e, n0;
     if (!mxm_tile_begin<DT, 64 * WN>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
-    mx6a6_gemm_tile<DT, MX6M6_WM, WN>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+    mx_scaled_gemm_tile<DT, MX6M6_WM, WN, mx_op_fp6, mx_op_fp6>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@
 // mxa8_quantize_kernel; codes, scale bytes, and the non-finite flag through the barrier) and reads neither xq nor a workspace.  Not
 // FUSED: it reads xq / xs / row_flag from memory.
 // Grouped prefill form: mxa8_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
-// mx6m_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx6a8_gemm_tile (mxfp6_common.cuh) at 128 x 64.  A row tile belongs to one
+// mx6m_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx_scaled_gemm_tile (mx_scaled_tile.cuh; FP6 x E4M3) at 128 x 64.  A row tile belongs to one
 // expert, gathers the xq / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the segment enter
 // as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no
 // K loop and store zeros.
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void mx6m_decode_kernel(const void* __restrict
 constexpr int MX6M_WM = 2, MX6M_WN = 1;
 static_assert(64 * MX6M_WM == MXM_BM, "a row tile of the routing is a row tile of the GEMM");
 
-// A workgroup per (row tile of the table, column tile): mx6a8_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
+// A workgroup per (row tile of the table, column tile): mx_scaled_gemm_tile on the tile's pairs and the expert's rows of the [E * N, K] view.
 template <int DT>
 __global__ __launch_bounds__(256) void mx6m_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                         const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void mx6m_gemm_kernel(const uint8_t* __restric
     __shared__ int prow[MXM_BM];
     int e, n0;
     if (!mxm_tile_begin<DT, 64 * MX6M_WN>(ws, max_tiles, E, N, y, prow, e, n0)) return;  // uniform
-    mx6a8_gemm_tile<DT, MX6M_WM, MX6M_WN>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
+    mx_scaled_gemm_tile<DT, MX6M_WM, MX6M_WN, mx_op_fp6, mx_op_e4m3>(mx_rows_listed{prow, S, x_per_pair}, xq, xs, row_flag, qw, sc, ecol, bias, y, (long)e * N, n0, N, K);
 }
 
 // ---- plan and launchers -------------------------------------------------------------------------------------------------------------------

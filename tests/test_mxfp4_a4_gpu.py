@@ -79,13 +79,14 @@ SHAPES = [(M, K, N) for M in (1, 2, 3, 8, 16, 17, 64) for K, N in ((32, 1), (96,
          [(M, K, N) for M in (1, 8, 16, 17, 64) for K, N in ((4096, 4096), (11008, 33), (96, 4096))] + \
          [(4096, 4096, 33), (4096, 96, 4096), (4096, 11008, 7), (4096, 4096, 4096)] + \
          [(M, K, N) for M in (32, 33, 65, 128, 129) for K, N in ((160, 70), (32, 130), (1056, 258))] + \
-         [(7, 4096, 11008), (64, 4096, 11008), (300, 4096, 11008)]
+         [(7, 4096, 11008), (64, 4096, 11008), (300, 4096, 11008)] + [(257, 160, 21846)]
 
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("M,K,N", SHAPES)
 def test_forward_every_form_against_float64(M, K, N, dt):
-    g = torch.Generator().manual_seed(M * 7 + K * 3 + N)
+    """(257, 160, 21846): 3 x 171 = 513 tiles of 128 x 128, the (2, 2) tile instance with ragged edges in M, N and K."""
+    g =torch.Generator().manual_seed(M * 7 + K * 3 + N)
     q, s = rand_mx(N, K, g)
     x = (torch.randn((M, K), generator=g) * 0.5).to(dt)
     bias = (torch.randn(N, generator=g)).to(dt) if (M + N) % 2 else None

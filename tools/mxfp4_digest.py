@@ -1,15 +1,21 @@
 #!/usr/bin/env python
-"""One SHA-256 of y's bytes per case for the four MXFP4 layers (weight-only and W4A4, linear and experts), every form forced: two builds
-of the library compute the same bits exactly when their listings are equal line for line.
+"""One SHA-256 of y's bytes per case for the MX layers, every form forced: the weight-only MXFP4 layers and every layer on the shared
+block-scaled tile (mx_scaled_gemm_tile: W4A4, W4A6, W4A8, W6A6, W6A8, W8A8 linear; W4A4, W4A6, W4A8, W6A6, W6A8 experts).  Two builds of
+the library compute the same bits exactly when their listings are equal line for line.
 
   python tools/mxfp4_digest.py > new.txt;  BIE_HIP_LIB=/path/to/other/libbie_hip.so python tools/mxfp4_digest.py > old.txt;  diff old.txt new.txt
 
 Every input comes from numpy.random.default_rng(seed) on the host, so both runs see the same bytes.  Cases: fp16 and bf16, bias on and
-off; the linear layers at M in {1, 16, 17, 64, 65, 300} on 96 -> 130 and 2880 -> 2880; the expert layers with x per token and per pair
-at E = 3, S = 4, 96 -> 33 (T in {1, 17, 300}) and E = 32, S = 4, 2880 -> 2880 (T in {16, 300})."""
+off; the linear layers at M in {1, 16, 17, 64, 65, 300} on 96 -> 130 and 2880 -> 2880, and at M = 257 on 160 -> 21846 (the 128 x 128
+tile instance with ragged M, N and K); the expert layers with x per token and per pair at E = 3, S = 4, 96 -> 33 (T in {1, 17, 300}) and
+E = 32, S = 4, 2880 -> 2880 (T in {16, 300}), and the two grouped A6 layers once more at E = 3, T = 300 under each value of their tile
+width knob (BIE_MXFP4_MOE_A6_WN, BIE_MXFP6_MOE_A6_WN)."""
 import hashlib
+import importlib
 import os
 import sys
+
+os.environ["BIE_TUNING"] = "1"  # read once, at the library's first call: the tile width knobs are then re-read on every call
 
 import numpy as np
 import torch
@@ -20,7 +26,20 @@ DEV = "cuda"
 DTS = ((torch.float16, "f16"), (torch.bfloat16, "bf16"))
 DENSE = ((96, 130), (2880, 2880))
 DENSE_M = (1, 16, 17, 64, 65, 300)
+DENSE_TILE128 = (257, 160, 21846)  # M, K, N
 EXPERTS = ((3, 4, 96, 33, (1, 17, 300)), (32, 4, 2880, 2880, (16, 300)))
+# (extension, name in the listing, bits per weight code, largest M of the decode form)
+LINEAR = (("mxfp4_linear_cuda", "linear", 4, 16), ("mxfp4_a4_linear_cuda", "linear_a4", 4, 64), ("mxfp4_a6_linear_cuda", "linear_a6", 4, 64),
+          ("mxfp4_a8_linear_cuda", "linear_a8", 4, 64), ("mxfp6_a6_linear_cuda", "linear_w6a6", 6, 64), ("mxfp6_a8_linear_cuda", "linear_w6a8", 6, 64),
+          ("mxfp8_a8_linear_cuda", "linear_w8a8", 8, 64))
+# (extension, name in the listing, bits per weight code, tile width knob or None)
+GROUPED = (("mxfp4_experts_cuda", "experts", 4, None), ("mxfp4_experts_a4_cuda", "experts_a4", 4, None),
+           ("mxfp4_experts_a6_cuda", "experts_a6", 4, "BIE_MXFP4_MOE_A6_WN"), ("mxfp4_experts_a8_cuda", "experts_a8", 4, None),
+           ("mxfp6_experts_a6_cuda", "experts_w6a6", 6, "BIE_MXFP6_MOE_A6_WN"), ("mxfp6_experts_a8_cuda", "experts_w6a8", 6, None))
+
+
+def ext(name):
+    return importlib.import_module("bitorch_engine.extensions." + name)
 
 
 def sha(y):
@@ -28,8 +47,16 @@ def sha(y):
     return hashlib.sha256(y.contiguous().view(torch.int16).cpu().numpy().tobytes()).hexdigest()
 
 
+def codes(rng, rows, K, bits):
+    """rows x (K * bits / 8) random code bytes; no E4M3 NaN code (0x7f, 0xff), which would hide a whole row of y"""
+    q = rng.integers(0, 256, (rows, K * bits // 8), dtype=np.uint8)
+    if bits == 8:
+        q[(q & 0x7F) == 0x7F] -= 1
+    return torch.from_numpy(q).to(DEV)
+
+
 def weights(rng, rows, K):
-    q = torch.from_numpy(rng.integers(0, 256, (rows, K // 2), dtype=np.uint8)).to(DEV)
+    q = codes(rng, rows, K, 4)
     s = torch.from_numpy(rng.integers(118, 131, (rows, K // 32), dtype=np.uint8)).to(DEV)
     return q, s
 
@@ -38,40 +65,62 @@ def normal(rng, shape, dt):
     return torch.from_numpy(rng.standard_normal(shape, dtype=np.float32)).to(dt).to(DEV)
 
 
-def main():
-    from bitorch_engine.extensions import mxfp4_a4_linear_cuda as a4, mxfp4_experts_a4_cuda as ma4, mxfp4_experts_cuda as moe, mxfp4_linear_cuda as mx
-    for K, N in DENSE:
-        rng = np.random.default_rng(1000 + K + N)
-        q, s = weights(rng, N, K)
-        e_col = mx.col_exp(s)
-        for dt, dname in DTS:
-            bias = normal(rng, (N,), dt)
-            for M in DENSE_M:
-                x = normal(rng, (M, K), dt)
+def dense(K, N, Ms):
+    rng = np.random.default_rng(1000 + K + N)
+    q4, s = weights(rng, N, K)
+    rng_w = np.random.default_rng(3000 + K + N)  # the wider codes from a stream of their own: the draws above stay as they were
+    q = {4: q4, 6: codes(rng_w, N, K, 6), 8: codes(rng_w, N, K, 8)}
+    e_col = ext("mxfp4_linear_cuda").col_exp(s)
+    for dt, dname in DTS:
+        bias = normal(rng, (N,), dt)
+        for M in Ms:
+            x = normal(rng, (M, K), dt)
+            for b, bname in ((None, "nobias"), (bias, "bias")):
+                for mod, name, bits, decode_rows in LINEAR:
+                    for form in (0, 1):
+                        if form == 0 and M > decode_rows:
+                            continue  # the decode form does not exist at this M
+                        print(f"{name} {dname} {bname} K={K} N={N} M={M} form={form} {sha(ext(mod).forward(x, q[bits], s, b, e_col, form=form))}")
+
+
+def grouped(E, S, K, N, Ts, knob_value=None):
+    rng = np.random.default_rng(2000 + E + K + N)
+    q4, s = weights(rng, E * N, K)
+    q = {4: q4.reshape(E, N, K // 2), 6: codes(np.random.default_rng(4000 + E + K + N), E * N, K, 6).reshape(E, N, K // 32 * 24)}
+    s = s.reshape(E, N, K // 32)
+    e_col = ext("mxfp4_experts_cuda").col_exp(s)
+    for dt, dname in DTS:
+        bias = normal(rng, (E, N), dt)
+        for T in Ts:
+            idx = torch.from_numpy(rng.integers(-1, E + 1, (T, S)).astype(np.int32)).to(DEV)  # -1 and E: skipped slots
+            xs = {0: normal(rng, (T, K), dt), 1: normal(rng, (T, S, K), dt)}
+            for xpp in (0, 1):
                 for b, bname in ((None, "nobias"), (bias, "bias")):
-                    for layer, name in ((mx, "linear"), (a4, "linear_a4")):
+                    for mod, name, bits, knob in GROUPED:
+                        if knob_value is not None:
+                            if knob is None:
+                                continue
+                            os.environ[knob] = str(knob_value)
+                            name = f"{name} wn={knob_value}"
                         for form in (0, 1):
-                            if form == 0 and M > (16 if layer is mx else 64):
-                                continue  # the decode form does not exist at this M
-                            print(f"{name} {dname} {bname} K={K} N={N} M={M} form={form} {sha(layer.forward(x, q, s, b, e_col, form=form))}")
+                            if form == 0 and (T * S > 1024 or knob_value is not None):
+                                continue  # the routed decode form does not exist at this P; the knob is the grouped form's
+                            y = ext(mod).forward(xs[xpp], idx, q[bits], s, b, e_col, form=form)
+                            print(f"{name} {dname} {bname} E={E} S={S} K={K} N={N} T={T} xpp={xpp} form={form} {sha(y)}")
+                        if knob_value is not None:
+                            del os.environ[knob]
+
+
+def main():
+    for K, N in DENSE:
+        dense(K, N, DENSE_M)
     for E, S, K, N, Ts in EXPERTS:
-        rng = np.random.default_rng(2000 + E + K + N)
-        q, s = weights(rng, E * N, K)
-        q, s = q.reshape(E, N, K // 2), s.reshape(E, N, K // 32)
-        e_col = moe.col_exp(s)
-        for dt, dname in DTS:
-            bias = normal(rng, (E, N), dt)
-            for T in Ts:
-                idx = torch.from_numpy(rng.integers(-1, E + 1, (T, S)).astype(np.int32)).to(DEV)  # -1 and E: skipped slots
-                xs = {0: normal(rng, (T, K), dt), 1: normal(rng, (T, S, K), dt)}
-                for xpp in (0, 1):
-                    for b, bname in ((None, "nobias"), (bias, "bias")):
-                        for layer, name in ((moe, "experts"), (ma4, "experts_a4")):
-                            for form in (0, 1):
-                                if form == 0 and T * S > 1024:
-                                    continue  # the routed decode form does not exist at this P
-                                y = layer.forward(xs[xpp], idx, q, s, b, e_col, form=form)
-                                print(f"{name} {dname} {bname} E={E} S={S} K={K} N={N} T={T} xpp={xpp} form={form} {sha(y)}")
+        grouped(E, S, K, N, Ts)
+    M, K, N = DENSE_TILE128
+    dense(K, N, (M,))
+    E, S, K, N, Ts = EXPERTS[0]
+    for wn in (1, 2):
+        grouped(E, S, K, N, Ts[-1:], knob_value=wn)
 
 
 if __name__ == "__main__":
