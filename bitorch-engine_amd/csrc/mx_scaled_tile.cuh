@@ -2,7 +2,8 @@
 // the grouped mxfp4_moe_a4 / _a6 / _a8, mxfp6_moe_a6 / _a8): the instructions' operand types, the three operand formats (FP4 E2M1, FP6
 // E2M3, FP8 E4M3) as the facts in which a kernel's handling of them differs, the store of four consecutive columns of one row of y, and
 // the one prefill tile body on v_mfma_scale_f32_32x32x64_f8f6f4 (mx_scaled_gemm_tile), parameterised on the formats of its two operands.
-// The quantisers' units stay with their formats (mxfp4_a4_common.cuh, mxfp4_a8_common.cuh, mxfp6_common.cuh).
+// The decode bodies on v_mfma_scale_f32_16x16x128_f8f6f4 are in mx_scaled_decode.cuh, on the same three format types.  The quantisers'
+// units and rows stay with their formats (mxfp4_a4_common.cuh, mxfp4_a8_common.cuh, mxfp6_common.cuh).
 #pragma once
 #include "mxfp4_common.cuh"
 
@@ -37,10 +38,20 @@ __device__ __forceinline__ mxa4_v8i a8_frag(const uint4_t& lo, const uint4_t& hi
     return mxa4_v8i{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
 }
 
+// a load of the weight stream (NT: non-temporal, every byte is read once) or of x
+template <bool NT, class T>
+__device__ __forceinline__ T mx_ld(const T* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
 // ---- the three operand formats ----------------------------------------------------------------------------------------------------------------
 // What the tile needs to know of an operand's format: the bytes of a block of 32 (BLOCK), the widest aligned piece a row can be copied
 // in (piece_t, PIECE bytes), the pitch of a row of a BK-k stage in LDS with the reason for its pad, how lane group hh's fragment of
-// k-step ks (64 k) is read from such a row, and the instruction's format code (cbsz for A, blgp for B).
+// k-step ks (64 k) is read from such a row, and the instruction's format code (cbsz for A, blgp for B).  The decode kernels
+// (mx_scaled_decode.cuh, 16x16x128: lane group kq of four, 128-k step s of a row held in memory) need which runs of the row make up a
+// lane's fragment: PARTS runs of part_t, run i in block part_block(s, kq, i) at byte part_off(kq) of that block.  The scale byte is
+// always that of block 4 s + kq.
 struct mx_op_fp4 {
     static constexpr int BLOCK = 16, PIECE = 16, CODE = 4;
     typedef uint4_t piece_t;
@@ -49,6 +60,13 @@ struct mx_op_fp4 {
     static __device__ __forceinline__ mxa4_v8i frag(const unsigned char* row, int ks, int hh) {
         return a4_frag(*reinterpret_cast<const uint4_t*>(row + (ks * 2 + hh) * 16));
     }
+    static constexpr int PARTS = 1;  // block 4 s + kq, whole
+    typedef uint4_t part_t;
+    static __device__ __forceinline__ int part_block(int s, int kq, int) { return 4 * s + kq; }
+    static __device__ __forceinline__ int part_off(int) { return 0; }
+    template <bool NT>
+    static __device__ __forceinline__ part_t part_load(const uint8_t* p) { return mx_ld<NT>(reinterpret_cast<const uint4_t*>(p)); }
+    static __device__ __forceinline__ mxa4_v8i lane_frag(const part_t (&v)[1]) { return a4_frag(v[0]); }
 };
 
 struct mx_op_fp6 {
@@ -66,6 +84,16 @@ struct mx_op_fp6 {
         const uint2_t* p = reinterpret_cast<const uint2_t*>(row + (ks * 2 + hh) * 24);
         return a6_frag(p[0], p[1], p[2]);
     }
+    static constexpr int PARTS = 1;  // block 4 s + kq, whole, in its three 8-byte pieces
+    struct part_t { uint2_t p0, p1, p2; };
+    static __device__ __forceinline__ int part_block(int s, int kq, int) { return 4 * s + kq; }
+    static __device__ __forceinline__ int part_off(int) { return 0; }
+    template <bool NT>
+    static __device__ __forceinline__ part_t part_load(const uint8_t* p) {
+        const uint2_t* q = reinterpret_cast<const uint2_t*>(p);
+        return part_t{mx_ld<NT>(q), mx_ld<NT>(q + 1), mx_ld<NT>(q + 2)};
+    }
+    static __device__ __forceinline__ mxa4_v8i lane_frag(const part_t (&v)[1]) { return a6_frag(v[0].p0, v[0].p1, v[0].p2); }
 };
 
 struct mx_op_e4m3 {
@@ -77,6 +105,13 @@ struct mx_op_e4m3 {
         const uint4_t* p = reinterpret_cast<const uint4_t*>(row + ks * 64 + hh * 16);
         return a8_frag(p[0], p[2]);  // bytes 16 hh .. + 15 of the step's first block and of its second (a8_frag)
     }
+    static constexpr int PARTS = 2;  // bytes 16 (kq & 1) .. + 15 of blocks 4 s + (kq >> 1) and + 2: each half has its own in-range test
+    typedef uint4_t part_t;
+    static __device__ __forceinline__ int part_block(int s, int kq, int i) { return 4 * s + (kq >> 1) + 2 * i; }
+    static __device__ __forceinline__ int part_off(int kq) { return 16 * (kq & 1); }
+    template <bool NT>
+    static __device__ __forceinline__ part_t part_load(const uint8_t* p) { return mx_ld<NT>(reinterpret_cast<const uint4_t*>(p)); }
+    static __device__ __forceinline__ mxa4_v8i lane_frag(const part_t (&v)[2]) { return a8_frag(v[0], v[1]); }
 };
 
 // ---- four consecutive columns of one row of y -------------------------------------------------------------------------------------------------

@@ -26,22 +26,13 @@
 namespace bie {
 
 // ---- activation quantiser -------------------------------------------------------------------------------------------------------------
-// Workgroup = one row.  Thread t takes the 8-value units t, t + 256, ... of the row; the 4 lanes of a quad hold one block of 32.
+// Workgroup = one row (mx_quantize_row of mxfp4_a4_common.cuh).
 template <int DT>
 __global__ __launch_bounds__(256) void mxa4_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ xq, uint8_t* __restrict__ xs,
                                                             uint8_t* __restrict__ row_flag, int K) {
     const long m = blockIdx.x;
-    const uint16_t* xr = x + m * K;
-    uint32_t* qr = reinterpret_cast<uint32_t*>(xq + m * (K >> 1));
-    uint8_t* sr = xs + m * (K >> 5);
-    const int U = K >> 3;  // a multiple of 4: whole quads are in or out
     int bad = 0;
-    for (int u = threadIdx.x; u < U; u += 256) {
-        uint32_t codes, scode;
-        a4_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
-        qr[u] = codes;
-        if ((u & 3) == 0) sr[u >> 2] = (uint8_t)scode;
-    }
+    mx_quantize_row<DT>(mx_op_fp4{}, x + m * K, K, xq + m * (K >> 1), xs + m * (K >> 5), bad);
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) row_flag[m] = (uint8_t)(bad ? 1 : 0);
 }

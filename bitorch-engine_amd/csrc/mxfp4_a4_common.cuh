@@ -1,8 +1,9 @@
 // The device-side piece shared by the W4A4 translation units (mxfp4_a4.hip, mxfp4_moe_a4.hip; gfx950): the activation quantiser's rule
-// for one 8-value unit, so that a kernel that quantises a row itself produces the bits of mxa4_quantize_kernel.  The operand types of
-// the block-scaled matrix instructions and the prefill tile body are those of mx_scaled_tile.cuh.
+// for one 8-value unit and for a row, so that a kernel that quantises a row itself produces the bits of mxa4_quantize_kernel.  The
+// operand types of the block-scaled matrix instructions and the prefill tile body are those of mx_scaled_tile.cuh, the shared decode
+// bodies those of mx_scaled_decode.cuh.
 #pragma once
-#include "mx_scaled_tile.cuh"
+#include "mx_scaled_decode.cuh"
 
 namespace bie {
 
@@ -43,6 +44,19 @@ __device__ __forceinline__ void a4_quantize_unit(const uint4_t& raw, int& bad, u
         scode = mx_block_scale(amax, inv);
 #pragma unroll
         for (int i = 0; i < 8; i++) codes |= (mx_round_e2m1(fabsf(v[i] * inv)) | ((__float_as_uint(v[i]) >> 28) & 8u)) << (4 * i);
+    }
+}
+
+// A row of x to MXFP4 (mx_quantize_row of mx_scaled_decode.cuh): a dword of codes per unit, the block's scale byte from the quad's lane 0.
+// U = K / 8 is a multiple of 4 and the stride is 256: whole quads are in or out.
+template <int DT>
+__device__ __forceinline__ void mx_quantize_row(mx_op_fp4, const uint16_t* xr, int K, uint8_t* codes, uint8_t* scales, int& bad) {
+    const int U = K >> 3;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint32_t c, scode;
+        a4_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
+        reinterpret_cast<uint32_t*>(codes)[u] = c;
+        if ((u & 3) == 0) scales[u >> 2] = (uint8_t)scode;
     }
 }
 

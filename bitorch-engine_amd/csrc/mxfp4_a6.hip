@@ -21,8 +21,8 @@
 // The one-hot selector test of tests/test_mxfp4_a6_gpu.py holds the element maps in the suite.
 //
 // There is no quantise kernel here: mxfp6_a6_quantize_launch is called as it stands.  Decode form (mx4a6_decode_kernel, M <= 64):
-// mxa8_decode_kernel's structure; a lane's weight fragment is one non-temporal 16-byte load and its x fragment its block's 24 bytes in
-// three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx_scaled_gemm_tile (FP4 x FP6) of mx_scaled_tile.cuh.
+// mx_scaled_decode_rows (FP4 x FP6) of mx_scaled_decode.cuh; a lane's weight fragment is one non-temporal 16-byte load and its x
+// fragment its block's 24 bytes in three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx_scaled_gemm_tile (FP4 x FP6) of mx_scaled_tile.cuh.
 #include "mxfp6_common.cuh"
 
 #pragma clang fp contract(off)
@@ -32,79 +32,12 @@ namespace bie {
 int mxfp6_a6_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);  // mxfp6_a6.hip
 
 // ---- decode form ------------------------------------------------------------------------------------------------------------------------
-// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
-// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15 and block l >> 4 of the step on both sides: 16 bytes of codes and a scale
-// byte of the weights, 24 bytes of codes and a scale byte of every 16-row group of x.  Blocks past K and rows past M enter as zero codes
-// under scale 2^0 (code 127).  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one row of y.
+// A workgroup per 16 output columns, M <= 16 G rows (mx_scaled_decode_rows).
 template <int DT, int G>
 __global__ __launch_bounds__(256) void mx4a6_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                            const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                            const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
-    __shared__ mxa4_v4f red[3][G][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int KB = K >> 5, KS = (KB + 3) >> 2;
-    const long xrowb = (long)KB * MX6_BLOCK_BYTES;
-    const int n0 = blockIdx.x * 16;
-    const long nl = min(n0 + r16, N - 1);
-    const uint8_t* wrow = qw + nl * (K >> 1);
-    const uint8_t* srow = sc + nl * KB;
-    mxa4_v4f acc[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
-    for (int s = wave; s < KS; s += 4) {
-        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
-        const bool kin = kb < KB;
-        uint4_t w = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow) + kc);
-        int sw = __builtin_nontemporal_load(srow + kc);
-        uint2_t a0[G], a1[G], a2[G];
-        int sa[G];
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const long m = min(g * 16 + r16, M - 1);
-            const uint2_t* xp = reinterpret_cast<const uint2_t*>(xq + m * xrowb + (long)kc * MX6_BLOCK_BYTES);
-            a0[g] = xp[0];
-            a1[g] = xp[1];
-            a2[g] = xp[2];
-            sa[g] = xs[m * KB + kc];
-        }
-        if (!kin) {
-            w = uint4_t{0u, 0u, 0u, 0u};
-            sw = 127;
-        }
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            if (!kin || g * 16 + r16 >= M) {
-                a0[g] = a1[g] = a2[g] = uint2_t{0u, 0u};
-                sa[g] = 127;
-            }
-        }
-        const mxa4_v8i fw = a4_frag(w);
-#pragma unroll
-        for (int g = 0; g < G; g++)
-            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, a6_frag(a0[g], a1[g], a2[g]), acc[g], 4, 2, 0, sw, 0, sa[g]);
-    }
-    if (wave) {
-#pragma unroll
-        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
-    }
-    __syncthreads();
-    if (wave) return;
-    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y (mx_store4)
-    const int n = n0 + 4 * kq;
-    if (n >= N) return;
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        const int m = g * 16 + r16;
-        if (m >= M) continue;
-        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
-        const bool rbad = row_flag[m] != 0;
-        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
-        mx_store4<DT>(v, rbad, ecol, bias, n, yr, n, N);
-    }
+    mx_scaled_decode_rows<DT, G, mx_op_fp4, mx_op_fp6>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K);
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------

@@ -20,9 +20,8 @@
 //
 // Quantise kernel (mxa8_quantize_kernel): a workgroup per row of x, a block of 32 per 4 lanes (16-byte loads, 8 bytes of codes per
 // lane), the block maximum over the 4 lanes on the DPP network, the row's non-finite flag through the workgroup's barrier.
-// Decode form (mxa8_decode_kernel, M <= 64): a workgroup per 16 output columns, K split over its 4 waves; every wave loads its weight
-// fragments straight from qweight (non-temporal, 16 bytes per lane) and the x fragments from xq (two 16-byte loads 64 bytes apart),
-// one 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS in a fixed order.
+// Decode form (mxa8_decode_kernel, M <= 64): mx_scaled_decode_rows (FP4 x E4M3) of mx_scaled_decode.cuh; a lane's weight fragment is
+// one non-temporal 16-byte load, its x fragment two 16-byte loads 64 bytes apart.
 // Prefill form (mxa8_gemm_kernel): mx_scaled_gemm_tile (FP4 x E4M3) of mx_scaled_tile.cuh, a (64 WM) x (64 WN) tile GEMM on 32x32x64, 4 waves as 2 x 2,
 // codes and scale bytes staged through registers into double-buffered LDS (128 k per stage), on the rows m0 .. of xq / xs.
 #include "mxfp4_a8_common.cuh"
@@ -32,102 +31,24 @@
 namespace bie {
 
 // ---- activation quantiser -------------------------------------------------------------------------------------------------------------
-// Workgroup = one row.  Thread t takes the 8-value units t, t + 256, ... of the row; the 4 lanes of a quad hold one block of 32.
+// Workgroup = one row (mx_quantize_row of mxfp4_a8_common.cuh).
 template <int DT>
 __global__ __launch_bounds__(256) void mxa8_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ xq, uint8_t* __restrict__ xs,
                                                             uint8_t* __restrict__ row_flag, int K) {
     const long m = blockIdx.x;
-    const uint16_t* xr = x + m * K;
-    uint2_t* qr = reinterpret_cast<uint2_t*>(xq + m * K);
-    uint8_t* sr = xs + m * (K >> 5);
-    const int U = K >> 3;  // a multiple of 4: whole quads are in or out
     int bad = 0;
-    for (int u = threadIdx.x; u < U; u += 256) {
-        uint2_t codes;
-        uint32_t scode;
-        a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
-        qr[u] = codes;
-        if ((u & 3) == 0) sr[u >> 2] = (uint8_t)scode;
-    }
+    mx_quantize_row<DT>(mx_op_e4m3{}, x + m * K, K, xq + m * K, xs + m * (K >> 5), bad);
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) row_flag[m] = (uint8_t)(bad ? 1 : 0);
 }
 
 // ---- decode form ------------------------------------------------------------------------------------------------------------------------
-// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
-// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15, block l >> 4 of the step's weights and x scales, and the x bytes
-// 16 (l >> 4) .. + 15 and 64 + 16 (l >> 4) .. + 15 of the step (a8_frag).  Blocks past K and rows past M enter as zero codes under
-// scale 2^0 (code 127).  The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one
-// row of y.
+// A workgroup per 16 output columns, M <= 16 G rows (mx_scaled_decode_rows).
 template <int DT, int G>
 __global__ __launch_bounds__(256) void mxa8_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                           const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                           const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
-    __shared__ mxa4_v4f red[3][G][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int KB = K >> 5, KS = (KB + 3) >> 2;
-    const int n0 = blockIdx.x * 16;
-    const long nl = min(n0 + r16, N - 1);
-    const uint8_t* wrow = qw + nl * (K >> 1);
-    const uint8_t* srow = sc + nl * KB;
-    mxa4_v4f acc[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
-    for (int s = wave; s < KS; s += 4) {
-        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
-        const bool kin = kb < KB;
-        uint4_t w = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow) + kc);
-        int sw = __builtin_nontemporal_load(srow + kc);
-        // this lane's x halves: 16 bytes of block b0 = kq >> 1 of the step and 16 bytes of block b0 + 2, at offset 16 (kq & 1) in each
-        const int kb0 = s * 4 + (kq >> 1), kb1 = kb0 + 2;
-        const bool in0 = kb0 < KB, in1 = kb1 < KB;
-        const int o0 = min(kb0, KB - 1) * 32 + (kq & 1) * 16, o1 = min(kb1, KB - 1) * 32 + (kq & 1) * 16;
-        uint4_t a0[G], a1[G];
-        int sa[G];
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const long m = min(g * 16 + r16, M - 1);
-            a0[g] = *reinterpret_cast<const uint4_t*>(xq + m * K + o0);
-            a1[g] = *reinterpret_cast<const uint4_t*>(xq + m * K + o1);
-            sa[g] = xs[m * KB + kc];
-        }
-        if (!kin) {
-            w = uint4_t{0u, 0u, 0u, 0u};
-            sw = 127;
-        }
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const bool dead = g * 16 + r16 >= M;
-            if (!in0 || dead) a0[g] = uint4_t{0u, 0u, 0u, 0u};
-            if (!in1 || dead) a1[g] = uint4_t{0u, 0u, 0u, 0u};
-            if (!kin || dead) sa[g] = 127;
-        }
-#pragma unroll
-        for (int g = 0; g < G; g++)
-            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(w), a8_frag(a0[g], a1[g]), acc[g], 4, 0, 0, sw, 0, sa[g]);
-    }
-    if (wave) {
-#pragma unroll
-        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
-    }
-    __syncthreads();
-    if (wave) return;
-    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y (mx_store4)
-    const int n = n0 + 4 * kq;
-    if (n >= N) return;
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        const int m = g * 16 + r16;
-        if (m >= M) continue;
-        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
-        const bool rbad = row_flag[m] != 0;
-        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
-        mx_store4<DT>(v, rbad, ecol, bias, n, yr, n, N);
-    }
+    mx_scaled_decode_rows<DT, G, mx_op_fp4, mx_op_e4m3>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K);
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------

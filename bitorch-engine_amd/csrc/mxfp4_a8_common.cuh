@@ -1,6 +1,6 @@
 // The device-side piece of the translation units with MXFP8 (E4M3) activations (mxfp4_a8.hip, mxfp4_moe_a8.hip, mxfp6_a8.hip,
-// mxfp6_moe_a8.hip, mxfp8_a8.hip; gfx950): the activation quantiser's rule for one 8-value unit, so that a kernel that quantises a row
-// itself (mxma8_decode_kernel) produces the bits of mxa8_quantize_kernel.  The E4M3 operand of the instructions (a8_frag, mx_op_e4m3) and
+// mxfp6_moe_a8.hip, mxfp8_a8.hip; gfx950): the activation quantiser's rule for one 8-value unit and for a row, so that a kernel that
+// quantises a row itself (mxma8_decode_kernel, mx6m_decode_kernel) produces the bits of mxa8_quantize_kernel.  The E4M3 operand of the instructions (a8_frag, mx_op_e4m3) and
 // the prefill tile body are those of mx_scaled_tile.cuh.
 #pragma once
 #include "mxfp4_a4_common.cuh"
@@ -60,6 +60,20 @@ __device__ __forceinline__ void a8_quantize_unit(const uint4_t& raw, int& bad, u
         hi = __builtin_amdgcn_cvt_pk_fp8_f32(a8_clamp(v[4], inv), a8_clamp(v[5], inv), hi, false);
         hi = __builtin_amdgcn_cvt_pk_fp8_f32(a8_clamp(v[6], inv), a8_clamp(v[7], inv), hi, true);
         codes = uint2_t{(uint32_t)lo, (uint32_t)hi};
+    }
+}
+
+// A row of x to MXFP8 (mx_quantize_row of mx_scaled_decode.cuh): 8 bytes of codes per unit, the block's scale byte from the quad's lane 0.
+// U = K / 8 is a multiple of 4 and the stride is 256: whole quads are in or out.
+template <int DT>
+__device__ __forceinline__ void mx_quantize_row(mx_op_e4m3, const uint16_t* xr, int K, uint8_t* codes, uint8_t* scales, int& bad) {
+    const int U = K >> 3;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint2_t c;
+        uint32_t scode;
+        a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
+        reinterpret_cast<uint2_t*>(codes)[u] = c;
+        if ((u & 3) == 0) scales[u >> 2] = (uint8_t)scode;
     }
 }
 

@@ -12,14 +12,10 @@
 // A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
 // row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
 //
-// Routed decode form (mxma8_decode_kernel, P <= 1024): a workgroup per pair and strip of 16 C16 columns of its expert, K split over the
-// 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4 in the operand order of mxfp4_a8.hip (the only one
-// profiles/mxfp4_a8_probe.txt pinned): the weight fragment is A (FP4, cbsz 4), the x fragment B (E4M3, blgp 0, the two halves of
-// a8_frag), byte select 0.  The pair's row is column 0 of B, so the lanes with (lane & 15) == 0 carry it; all other columns are zero
-// codes under scale code 127.  The four partial sums meet in LDS and are summed as ((w0 + w1) + w2) + w3, the order of
-// mxa8_decode_kernel: a pair's row has the bits of the dense W4A8 decode form.  FUSED (one launch, K <= MXMA8_ONE_K): the workgroup
-// quantises x_row(p) into LDS itself (a8_quantize_unit, the bits of mxa8_quantize_kernel; codes, scale bytes, and the non-finite flag
-// through the barrier) and reads neither xq nor a workspace.  Not FUSED: it reads xq / xs / row_flag from memory.
+// Routed decode form (mxma8_decode_kernel, P <= 1024): mx_scaled_decode_pair (FP4 x E4M3) of mx_scaled_decode.cuh, in the operand
+// order of mxfp4_a8.hip (the only one profiles/mxfp4_a8_probe.txt pinned): the weight fragment is A (FP4, cbsz 4), the x fragment B
+// (E4M3, blgp 0, the two halves of a8_frag), byte select 0; a pair's row has the bits of the dense W4A8 decode form.  FUSED (one
+// launch, K <= MXMA8_ONE_K): the row image in LDS is written by mx_quantize_row, which mxa8_quantize_kernel calls too.
 // Grouped prefill form: mxa8_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
 // mxma8_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx_scaled_gemm_tile (mx_scaled_tile.cuh; FP4 x E4M3) at 128 x 128.  A row tile belongs to one
 // expert, gathers the xq / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the segment enter
@@ -43,115 +39,13 @@ int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, 
 constexpr int MXMA8_ONE_K = 16384;
 constexpr int MXMA8_DECODE_PAIRS = 1024;  // the grid's second dimension
 
-// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
-// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step's weights; the lanes
-// with (l & 15) == 0 hold the x bytes 16 (l >> 4) .. + 15 and 64 + 16 (l >> 4) .. + 15 of the step and the x scale of block l >> 4.
-// xin is x (FUSED) or xq.
+// A workgroup per pair and strip of 16 C16 columns of its expert (mx_scaled_decode_pair).  xin is x (FUSED) or the quantised rows.
 template <int DT, int C16, bool FUSED>
 __global__ __launch_bounds__(256) void mxma8_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                            const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
                                                            const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
                                                            int N, int K, int x_per_pair) {
-    constexpr int C = 16 * C16;
-    __shared__ float red[4][C];
-    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MXMA8_ONE_K + MXMA8_ONE_K / 32 : 16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int p = blockIdx.y, n0 = blockIdx.x * C;
-    const int e = idx[p];
-    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
-        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
-        return;
-    }
-    const int KB = K >> 5, KS = (KB + 3) >> 2;
-    const long xrow = x_per_pair ? p : p / S;
-    const uint8_t* xqr = nullptr;
-    const uint8_t* xsr = nullptr;
-    int flagged;
-    if constexpr (FUSED) {
-        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
-        const int U = K >> 3;  // a multiple of 4: whole quads are in or out
-        int bad = 0;
-        for (int u = t; u < U; u += 256) {
-            uint2_t codes;
-            uint32_t scode;
-            a8_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, codes, scode);
-            reinterpret_cast<uint2_t*>(img)[u] = codes;
-            if ((u & 3) == 0) img[K + (u >> 2)] = (unsigned char)scode;
-        }
-        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
-    } else {
-        xqr = reinterpret_cast<const uint8_t*>(xin) + xrow * K;
-        xsr = xs + xrow * KB;
-        flagged = row_flag[xrow];
-    }
-    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
-    const uint8_t* wrow[C16];
-    const uint8_t* srow[C16];
-#pragma unroll
-    for (int c = 0; c < C16; c++) {
-        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
-        wrow[c] = qw + n * (K >> 1);
-        srow[c] = sc + n * KB;
-    }
-    mxa4_v4f acc[C16];
-#pragma unroll
-    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
-    for (int s = wave; s < KS; s += 4) {
-        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
-        const bool kin = kb < KB;
-        uint4_t w[C16];
-        int sw[C16];
-#pragma unroll
-        for (int c = 0; c < C16; c++) {
-            w[c] = __builtin_nontemporal_load(reinterpret_cast<const uint4_t*>(wrow[c]) + kc);
-            sw[c] = __builtin_nontemporal_load(srow[c] + kc);
-        }
-        // this lane's x halves: 16 bytes of block kq >> 1 of the step and 16 bytes of that block + 2, at offset 16 (kq & 1) in each
-        const int kb0 = s * 4 + (kq >> 1), kb1 = kb0 + 2;
-        uint4_t a0 = uint4_t{0u, 0u, 0u, 0u}, a1 = uint4_t{0u, 0u, 0u, 0u};
-        int sa = 127;
-        if (r16 == 0) {
-            const int o0 = kb0 * 32 + (kq & 1) * 16, o1 = kb1 * 32 + (kq & 1) * 16;
-            if constexpr (FUSED) {
-                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(img + o0);
-                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(img + o1);
-                if (kin) sa = img[K + kb];
-            } else {
-                if (kb0 < KB) a0 = *reinterpret_cast<const uint4_t*>(xqr + o0);
-                if (kb1 < KB) a1 = *reinterpret_cast<const uint4_t*>(xqr + o1);
-                if (kin) sa = xsr[kb];
-            }
-        }
-        if (!kin) {
-#pragma unroll
-            for (int c = 0; c < C16; c++) {
-                w[c] = uint4_t{0u, 0u, 0u, 0u};
-                sw[c] = 127;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < C16; c++)
-            acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a4_frag(w[c]), a8_frag(a0, a1), acc[c], 4, 0, 0, sw[c], 0, sa);
-    }
-    // C/D: D column (= row of the x operand) = lane & 15, D row (= column n of the strip) = 4 (lane >> 4) + r: the pair's row is
-    // registers 0 .. 3 of lanes 0, 16, 32, 48
-    if (r16 == 0) {
-#pragma unroll
-        for (int c = 0; c < C16; c++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) red[wave][c * 16 + 4 * kq + r] = acc[c][r];
-    }
-    __syncthreads();
-    if (t < C) {
-        const int n = n0 + t;
-        if (n < N) {
-            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
-            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
-            dt_traits<DT>::store(y, (long)p * N + n, v);
-        }
-    }
+    mx_scaled_decode_pair<DT, C16, FUSED, mx_op_fp4, mx_op_e4m3, MXMA8_ONE_K>(xin, xs, row_flag, idx, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair);
 }
 
 // ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------

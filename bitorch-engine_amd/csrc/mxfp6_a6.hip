@@ -22,8 +22,8 @@
 // Quantise kernel (mx6a6_quantize_kernel): a workgroup per row of x, a block of 32 per 4 lanes (16-byte loads), the block maximum over
 // the quad on the DPP network, 48 bits of codes per lane; lane i < 3 of a quad takes its right neighbour's 48 bits over the DPP network
 // and stores the i-th 8 bytes of the block; the row's non-finite flag through the workgroup's barrier.
-// Decode form (mx6a6_decode_kernel, M <= 64): mx6a8_decode_kernel's structure; a lane's x fragment is its block's 24 bytes in three
-// 8-byte loads, as its weight fragment is.  Prefill form (mx6a6_gemm_kernel): mx_scaled_gemm_tile (FP6 x FP6) of mx_scaled_tile.cuh.
+// Decode form (mx6a6_decode_kernel, M <= 64): mx_scaled_decode_rows (FP6 x FP6) of mx_scaled_decode.cuh; a lane's x fragment is its
+// block's 24 bytes in three 8-byte loads, as its weight fragment is (non-temporal).  Prefill form (mx6a6_gemm_kernel): mx_scaled_gemm_tile (FP6 x FP6) of mx_scaled_tile.cuh.
 #include "mxfp6_common.cuh"
 
 #pragma clang fp contract(off)
@@ -31,113 +31,25 @@
 namespace bie {
 
 // ---- activation quantiser -------------------------------------------------------------------------------------------------------------
-// Workgroup = one row.  Thread t takes the 8-value units t, t + 256, ... of the row; the 4 lanes of a quad hold one block of 32, lane q
-// bits 48 q .. 48 q + 47 of its 192.  The block's 8-byte word i is (c_i >> 16 i) | (c_(i+1) << (48 - 16 i)): lanes 0 .. 2 of the quad
-// store one word each, 24 contiguous bytes per quad.
+// Workgroup = one row (mx_quantize_row of mxfp6_common.cuh).
 template <int DT>
 __global__ __launch_bounds__(256) void mx6a6_quantize_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ xq, uint8_t* __restrict__ xs,
                                                              uint8_t* __restrict__ row_flag, int K) {
     const long m = blockIdx.x;
     const int KB = K >> 5;
-    const uint16_t* xr = x + m * K;
-    uint8_t* qr = xq + m * ((long)KB * MX6_BLOCK_BYTES);
-    uint8_t* sr = xs + m * KB;
-    const int U = K >> 3;  // a multiple of 4: whole quads are in or out
     int bad = 0;
-    for (int u = threadIdx.x; u < U; u += 256) {
-        uint64_t c;
-        uint32_t scode;
-        a6_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
-        // the right neighbour's codes: quad_perm [1, 2, 3, 0]
-        const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)c, 0x39, 0xf, 0xf, false);
-        const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(c >> 32), 0x39, 0xf, 0xf, false);
-        const uint64_t nb = (uint64_t)nlo | ((uint64_t)nhi << 32);
-        const int q = u & 3;
-        if (q < 3) {
-            const uint64_t word = (c >> (16 * q)) | (nb << (48 - 16 * q));
-            *reinterpret_cast<uint2_t*>(qr + (long)(u >> 2) * MX6_BLOCK_BYTES + q * 8) = uint2_t{(uint32_t)word, (uint32_t)(word >> 32)};
-        }
-        if (q == 0) sr[u >> 2] = (uint8_t)scode;
-    }
+    mx_quantize_row<DT>(mx_op_fp6{}, x + m * K, K, xq + m * ((long)KB * MX6_BLOCK_BYTES), xs + m * KB, bad);
     bad = __syncthreads_or(bad);
     if (threadIdx.x == 0) row_flag[m] = (uint8_t)(bad ? 1 : 0);
 }
 
 // ---- decode form ------------------------------------------------------------------------------------------------------------------------
-// Workgroup: columns 16 * blockIdx.x .. + 15 (reads past N clamped, never stored), rows 0 .. M - 1 (M <= 16 G).  Wave w takes the
-// 128-k steps w, w + 4, ...; lane l holds column (row) l & 15 and block l >> 4 of the step on both sides: 24 bytes of codes and a scale
-// byte of the weights, and of every 16-row group of x.  Blocks past K and rows past M enter as zero codes under scale 2^0 (code 127).
-// The weight fragment is the A operand, so a lane's accumulator holds 4 consecutive columns of one row of y.
+// A workgroup per 16 output columns, M <= 16 G rows (mx_scaled_decode_rows).
 template <int DT, int G>
 __global__ __launch_bounds__(256) void mx6a6_decode_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                            const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol,
                                                            const void* __restrict__ bias, void* __restrict__ y, int M, int N, int K) {
-    __shared__ mxa4_v4f red[3][G][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int KB = K >> 5, KS = (KB + 3) >> 2;
-    const long rowb = (long)KB * MX6_BLOCK_BYTES;
-    const int n0 = blockIdx.x * 16;
-    const long nl = min(n0 + r16, N - 1);
-    const uint8_t* wrow = qw + nl * rowb;
-    const uint8_t* srow = sc + nl * KB;
-    mxa4_v4f acc[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) acc[g] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
-    for (int s = wave; s < KS; s += 4) {
-        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // loads are clamped and unconditional, then masked
-        const bool kin = kb < KB;
-        const uint2_t* wp = reinterpret_cast<const uint2_t*>(wrow + (long)kc * MX6_BLOCK_BYTES);
-        uint2_t w0 = __builtin_nontemporal_load(wp), w1 = __builtin_nontemporal_load(wp + 1), w2 = __builtin_nontemporal_load(wp + 2);
-        int sw = __builtin_nontemporal_load(srow + kc);
-        uint2_t a0[G], a1[G], a2[G];
-        int sa[G];
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const long m = min(g * 16 + r16, M - 1);
-            const uint2_t* xp = reinterpret_cast<const uint2_t*>(xq + m * rowb + (long)kc * MX6_BLOCK_BYTES);
-            a0[g] = xp[0];
-            a1[g] = xp[1];
-            a2[g] = xp[2];
-            sa[g] = xs[m * KB + kc];
-        }
-        if (!kin) {
-            w0 = w1 = w2 = uint2_t{0u, 0u};
-            sw = 127;
-        }
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            if (!kin || g * 16 + r16 >= M) {
-                a0[g] = a1[g] = a2[g] = uint2_t{0u, 0u};
-                sa[g] = 127;
-            }
-        }
-        const mxa4_v8i fw = a6_frag(w0, w1, w2);
-#pragma unroll
-        for (int g = 0; g < G; g++)
-            acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, a6_frag(a0[g], a1[g], a2[g]), acc[g], 2, 2, 0, sw, 0, sa[g]);
-    }
-    if (wave) {
-#pragma unroll
-        for (int g = 0; g < G; g++) red[wave - 1][g][lane] = acc[g];
-    }
-    __syncthreads();
-    if (wave) return;
-    // C/D: D column (= row m of the 16) = lane & 15, D row (= column n of y) = 4 (lane >> 4) + r: four consecutive n of one row of y (mx_store4)
-    const int n = n0 + 4 * kq;
-    if (n >= N) return;
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        const int m = g * 16 + r16;
-        if (m >= M) continue;
-        const mxa4_v4f p1 = red[0][g][lane], p2 = red[1][g][lane], p3 = red[2][g][lane];
-        const bool rbad = row_flag[m] != 0;
-        uint16_t* yr = reinterpret_cast<uint16_t*>(y) + (long)m * N;
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) v[r] = ((acc[g][r] + p1[r]) + p2[r]) + p3[r];
-        mx_store4<DT>(v, rbad, ecol, bias, n, yr, n, N);
-    }
+    mx_scaled_decode_rows<DT, G, mx_op_fp6, mx_op_fp6>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K);
 }
 
 // ---- prefill form -----------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // The MXFP6 (OCP microscaling FP6, E2M3 elements) format's device-side rules (gfx950): the quantiser's rounding rule, code <-> fp32,
 // a block's 24 bytes <-> its 32 codes, the input-gradient 128 x 128 tile body (mx6_dgrad_tile: the kernels of mxfp6_grad.hip), the
-// weight-only (W6A16) 128 x 128 tile body (mx6_gemm_tile: mx6_gemm_kernel of mxfp6.hip) and the MXFP6 activation quantiser's unit
-// (a6_quantize_unit: the kernels of mxfp6_a6.hip, mxfp6_moe_a6.hip and mxfp4_moe_a6.hip).  The E8M0 block scales, the block-scale rule (mx_block_scale:
+// weight-only (W6A16) 128 x 128 tile body (mx6_gemm_tile: mx6_gemm_kernel of mxfp6.hip) and the MXFP6 activation quantiser's unit and
+// row (a6_quantize_unit, mx_quantize_row: the kernels of mxfp6_a6.hip, mxfp6_moe_a6.hip and mxfp4_moe_a6.hip).  The E8M0 block scales, the block-scale rule (mx_block_scale:
 // emax = 2 for E2M3 as for E2M1), the row sources and the MXFP8 activations are those of mxfp4_common.cuh / mxfp4_a8_common.cuh; the
 // FP6 operand of the block-scaled matrix instructions (a6_frag, mx_op_fp6) and the prefill tile body of the W6A8, W6A6 and W4A6 units
 // are those of mx_scaled_tile.cuh.
@@ -83,6 +83,30 @@ __device__ __forceinline__ void a6_quantize_unit(const uint4_t& raw, int& bad, u
 #pragma unroll
         for (int i = 0; i < 8; i++)
             codes |= (uint64_t)(mx6_round_e2m3(fminf(fabsf(v[i] * inv), 7.5f)) | ((__float_as_uint(v[i]) >> 26) & 32u)) << (6 * i);
+    }
+}
+
+// A row of x to MXFP6 (mx_quantize_row of mx_scaled_decode.cuh).  Lane q of a quad holds bits 48 q .. 48 q + 47 of its block's 192; the
+// block's 8-byte word i is (c_i >> 16 i) | (c_(i+1) << (48 - 16 i)): lane i < 3 takes its right neighbour's 48 bits over the DPP network
+// and stores word i, 24 contiguous bytes per quad; lane 0 stores the scale byte.  U = K / 8 is a multiple of 4 and the stride is 256:
+// whole quads are in or out, so the quad's exchanges are complete.
+template <int DT>
+__device__ __forceinline__ void mx_quantize_row(mx_op_fp6, const uint16_t* xr, int K, uint8_t* codes, uint8_t* scales, int& bad) {
+    const int U = K >> 3;
+    for (int u = threadIdx.x; u < U; u += 256) {
+        uint64_t c;
+        uint32_t scode;
+        a6_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
+        // the right neighbour's codes: quad_perm [1, 2, 3, 0]
+        const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)c, 0x39, 0xf, 0xf, false);
+        const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(c >> 32), 0x39, 0xf, 0xf, false);
+        const uint64_t nb = (uint64_t)nlo | ((uint64_t)nhi << 32);
+        const int q = u & 3;
+        if (q < 3) {
+            const uint64_t word = (c >> (16 * q)) | (nb << (48 - 16 * q));
+            *reinterpret_cast<uint2_t*>(codes + (long)(u >> 2) * MX6_BLOCK_BYTES + q * 8) = uint2_t{(uint32_t)word, (uint32_t)(word >> 32)};
+        }
+        if (q == 0) scales[u >> 2] = (uint8_t)scode;
     }
 }
 

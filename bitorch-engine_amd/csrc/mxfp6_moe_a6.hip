@@ -15,16 +15,11 @@
 // A row of y is a function of its own pair only: in both forms a row's sum runs over K in an order fixed by K alone.  Every expert and
 // row offset is 64-bit.  Nothing synchronises with the host: the grids are sized from P and E.
 //
-// Routed decode form (mx6m6_decode_kernel, P <= 1024): mx6m_decode_kernel's structure (mxfp6_moe_a8.hip): a workgroup per pair and strip
-// of 16 C16 columns of its expert, K split over the 4 waves in 128-k steps, on v_mfma_scale_f32_16x16x128_f8f6f4 with two FP6 operands
-// (cbsz 2, blgp 2, byte select 0; profiles/mxfp6_a6_probe.txt): the weight fragment is A (three non-temporal 8-byte pieces at
-// row * KB * 24 + block * 24), the x fragment B, and it is the same 24-byte copy: the lanes with (lane & 15) == 0 hold block lane >> 4
-// of the step of the pair's row (column 0 of B) with its scale byte; all other columns, and blocks past K on either side, are zero
-// codes under scale code 127.  The four partial sums meet in LDS and are summed as ((w0 + w1) + w2) + w3, the order of
-// mx6a6_decode_kernel: a pair's row has the bits of the dense W6A6 decode form.
-// FUSED (one launch, K <= MX6M6_ONE_K): the workgroup quantises x_row(p) into LDS itself (a6_quantize_unit and the quad-neighbour
-// exchange of mx6a6_quantize_kernel: the bits of bie_mxfp6_quantize_act; 3K/4 code bytes, K/32 scale bytes, the non-finite flag through
-// the barrier) and reads neither xq6 nor a workspace.  Not FUSED: it reads xq6 / xs / row_flag from memory.
+// Routed decode form (mx6m6_decode_kernel, P <= 1024): mx_scaled_decode_pair (FP6 x FP6) of mx_scaled_decode.cuh, with two FP6
+// operands (cbsz 2, blgp 2, byte select 0; profiles/mxfp6_a6_probe.txt): the weight fragment is three non-temporal 8-byte pieces, the x
+// fragment the same 24-byte copy of its block; a pair's row has the bits of the dense W6A6 decode form.  FUSED (one launch,
+// K <= MX6M6_ONE_K): the row image in LDS (3K/4 code bytes, K/32 scale bytes) is written by mx_quantize_row, which
+// mx6a6_quantize_kernel calls too: the bits of bie_mxfp6_quantize_act.
 // Grouped prefill form: mx6a6_quantize_kernel over the stored rows, mxm_route_kernel (mxfp4_moe.hip; the same workspace), then
 // mx6m6_gemm_kernel: mxm_tile_begin (mxfp4_common.cuh) and mx_scaled_gemm_tile (mx_scaled_tile.cuh; FP6 x FP6) at 128 x 128 or 128 x 64.  A row tile
 // belongs to one expert, gathers the xq6 / xs rows of its pairs through the pair list and reads weights from (long)e * N; rows past the
@@ -46,127 +41,15 @@ int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, 
 // The largest K of the one-launch form, the sibling expert kernels' bound.  A row's image in LDS is 3K/4 code bytes and K/32 scale
 // bytes: 12800 bytes at the bound (the W6A8 expert kernel's image is K + K/32 = 16896).
 constexpr int MX6M6_ONE_K = 16384;
-constexpr int MX6M6_IMG_CODES = MX6M6_ONE_K / 32 * MX6_BLOCK_BYTES;  // 12288
-constexpr int MX6M6_DECODE_PAIRS = 1024;                             // the grid's second dimension
-static_assert(MX6M6_IMG_CODES + MX6M6_ONE_K / 32 == 12800, "the row image of the one-launch form");
+constexpr int MX6M6_DECODE_PAIRS = 1024;  // the grid's second dimension
 
-// Workgroup: pair blockIdx.y, columns 16 C16 blockIdx.x .. + 16 C16 - 1 of its expert (reads past N clamped, never stored).  Wave w takes
-// the 128-k steps w, w + 4, ...; lane l holds column l & 15 of each of the C16 groups and block l >> 4 of the step's weights; the lanes
-// with (l & 15) == 0 hold the same block of the pair's row of x, 24 bytes and a scale byte.  xin is x (FUSED) or xq6.
+// A workgroup per pair and strip of 16 C16 columns of its expert (mx_scaled_decode_pair).  xin is x (FUSED) or the quantised rows.
 template <int DT, int C16, bool FUSED>
 __global__ __launch_bounds__(256) void mx6m6_decode_kernel(const void* __restrict__ xin, const uint8_t* __restrict__ xs, const uint8_t* __restrict__ row_flag,
                                                            const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw, const uint8_t* __restrict__ sc,
                                                            const uint8_t* __restrict__ ecol, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
                                                            int N, int K, int x_per_pair) {
-    constexpr int C = 16 * C16;
-    __shared__ float red[4][C];
-    __shared__ __attribute__((aligned(16))) unsigned char img[FUSED ? MX6M6_IMG_CODES + MX6M6_ONE_K / 32 : 16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int p = blockIdx.y, n0 = blockIdx.x * C;
-    const int e = idx[p];
-    if ((unsigned)e >= (unsigned)E) {  // a skipped slot (uniform): zeros, and no address is formed from e
-        if (t < C && n0 + t < N) dt_traits<DT>::store(y, (long)p * N + n0 + t, 0.0f);
-        return;
-    }
-    const int KB = K >> 5, KS = (KB + 3) >> 2;
-    const long rowb = (long)KB * MX6_BLOCK_BYTES;
-    const long xrow = x_per_pair ? p : p / S;
-    const unsigned char* xqr;  // the row's code bytes: the LDS image or xq6
-    const unsigned char* xsr;  // its scale bytes
-    int flagged;
-    if constexpr (FUSED) {
-        const uint16_t* xr = reinterpret_cast<const uint16_t*>(xin) + xrow * K;
-        const int U = K >> 3;  // a multiple of 4 and the stride is 256: whole quads are in or out, so the quad's exchanges are complete
-        int bad = 0;
-        for (int u = t; u < U; u += 256) {
-            uint64_t c;
-            uint32_t scode;
-            a6_quantize_unit<DT>(*reinterpret_cast<const uint4_t*>(xr + (long)u * 8), bad, c, scode);
-            // the right neighbour's codes: quad_perm [1, 2, 3, 0] (mx6a6_quantize_kernel)
-            const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)c, 0x39, 0xf, 0xf, false);
-            const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(c >> 32), 0x39, 0xf, 0xf, false);
-            const uint64_t nb = (uint64_t)nlo | ((uint64_t)nhi << 32);
-            const int q = u & 3;
-            if (q < 3) {
-                const uint64_t word = (c >> (16 * q)) | (nb << (48 - 16 * q));
-                *reinterpret_cast<uint2_t*>(img + (u >> 2) * MX6_BLOCK_BYTES + q * 8) = uint2_t{(uint32_t)word, (uint32_t)(word >> 32)};
-            }
-            if (q == 0) img[KB * MX6_BLOCK_BYTES + (u >> 2)] = (unsigned char)scode;
-        }
-        flagged = __syncthreads_or(bad);  // the barrier that publishes the image
-        xqr = img;
-        xsr = img + KB * MX6_BLOCK_BYTES;
-    } else {
-        xqr = reinterpret_cast<const unsigned char*>(xin) + xrow * rowb;
-        xsr = xs + xrow * KB;
-        flagged = row_flag[xrow];
-    }
-    const long r0 = (long)e * N;  // the expert's first row of the [E * N, K] view
-    const uint8_t* wrow[C16];
-    const uint8_t* srow[C16];
-#pragma unroll
-    for (int c = 0; c < C16; c++) {
-        const long n = r0 + min(n0 + c * 16 + r16, N - 1);
-        wrow[c] = qw + n * rowb;
-        srow[c] = sc + n * KB;
-    }
-    mxa4_v4f acc[C16];
-#pragma unroll
-    for (int c = 0; c < C16; c++) acc[c] = mxa4_v4f{0.f, 0.f, 0.f, 0.f};
-    for (int s = wave; s < KS; s += 4) {
-        const int kb = s * 4 + kq, kc = min(kb, KB - 1);  // weight loads are clamped and unconditional, then masked
-        const bool kin = kb < KB;
-        uint2_t w0[C16], w1[C16], w2[C16];
-        int sw[C16];
-#pragma unroll
-        for (int c = 0; c < C16; c++) {
-            const uint2_t* wp = reinterpret_cast<const uint2_t*>(wrow[c] + (long)kc * MX6_BLOCK_BYTES);
-            w0[c] = __builtin_nontemporal_load(wp);
-            w1[c] = __builtin_nontemporal_load(wp + 1);
-            w2[c] = __builtin_nontemporal_load(wp + 2);
-            sw[c] = __builtin_nontemporal_load(srow[c] + kc);
-        }
-        // this lane's x fragment: block kb of the pair's row in column 0, zero codes under scale 2^0 everywhere else
-        uint2_t a0 = uint2_t{0u, 0u}, a1 = uint2_t{0u, 0u}, a2 = uint2_t{0u, 0u};
-        int sa = 127;
-        if (r16 == 0 && kin) {
-            const uint2_t* xp = reinterpret_cast<const uint2_t*>(xqr + (long)kb * MX6_BLOCK_BYTES);
-            a0 = xp[0];
-            a1 = xp[1];
-            a2 = xp[2];
-            sa = xsr[kb];
-        }
-        if (!kin) {
-#pragma unroll
-            for (int c = 0; c < C16; c++) {
-                w0[c] = w1[c] = w2[c] = uint2_t{0u, 0u};
-                sw[c] = 127;
-            }
-        }
-        const mxa4_v8i fx = a6_frag(a0, a1, a2);
-#pragma unroll
-        for (int c = 0; c < C16; c++)
-            acc[c] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a6_frag(w0[c], w1[c], w2[c]), fx, acc[c], 2, 2, 0, sw[c], 0, sa);
-    }
-    // C/D: D column (= row of the x operand) = lane & 15, D row (= column n of the strip) = 4 (lane >> 4) + r: the pair's row is
-    // registers 0 .. 3 of lanes 0, 16, 32, 48
-    if (r16 == 0) {
-#pragma unroll
-        for (int c = 0; c < C16; c++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) red[wave][c * 16 + 4 * kq + r] = acc[c][r];
-    }
-    __syncthreads();
-    if (t < C) {
-        const int n = n0 + t;
-        if (n < N) {
-            float v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-            if (flagged || ecol[r0 + n] == 255u) v = a4_nan();
-            if (bias) v += dt_traits<DT>::load(bias, r0 + n);
-            dt_traits<DT>::store(y, (long)p * N + n, v);
-        }
-    }
+    mx_scaled_decode_pair<DT, C16, FUSED, mx_op_fp6, mx_op_fp6, MX6M6_ONE_K>(xin, xs, row_flag, idx, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair);
 }
 
 // ---- grouped prefill form: the GEMM -------------------------------------------------------------------------------------------------------

@@ -79,7 +79,7 @@ SHAPES = [(M, K, N) for M in (1, 2, 3, 8, 16, 17, 64) for K, N in ((32, 1), (96,
          [(M, K, N) for M in (1, 8, 16, 17, 64) for K, N in ((4096, 4096), (11008, 33), (96, 4096))] + \
          [(4096, 4096, 33), (4096, 96, 4096), (4096, 11008, 7), (4096, 4096, 4096)] + \
          [(M, K, N) for M in (32, 33, 65, 128, 129) for K, N in ((160, 70), (32, 130), (1056, 258))] + \
-         [(7, 4096, 11008), (64, 4096, 11008), (300, 4096, 11008)] + [(257, 160, 21846)]
+         [(7, 4096, 11008), (64, 4096, 11008), (300, 4096, 11008)] + [(257, 160, 21846)] + [(33, 96, 130)]
 
 
 @pytest.mark.parametrize("dt", DTS)

@@ -125,7 +125,7 @@ def test_selector_weights_pin_the_k_of_every_operand_byte(K, dt):
             assert torch.equal(y.cpu(), want), (M, form, (y.cpu() != want).nonzero()[:5].tolist())
 
 
-SHAPES = [(M, K, N) for M in (1, 2, 15, 16, 17, 32, 33, 64) for K, N in ((32, 1), (96, 7), (160, 70), (640, 17), (4096, 33))]
+SHAPES = [(M, K, N) for M in (1, 2, 15, 16, 17, 32, 33, 64) for K, N in ((32, 1), (96, 7), (160, 70), (640, 17), (4096, 33))] + [(33, 96, 130)]
 PREFILL_SHAPES = [(M, K, N) for M in (65, 129, 257) for K, N in ((160, 70), (32, 130), (1056, 258))] + [(257, 160, 21846)]
 
 

@@ -202,6 +202,25 @@ def test_gemm_on_chosen_codes_and_forward_is_quantize_then_gemm(K, form, xpp, dt
 
 
 @pytest.mark.parametrize("dt", DTS)
+def test_gemm_routed_form_on_a_small_ragged_case_against_float64(dt):
+    """E = 3, S = 4, T = 17, 96 -> 33, x per pair, form 0 of gemm: the routed kernel that reads the quantised rows from memory (forward
+    never runs it at this K), with K = 96 (one 128-k step whose last block lies past K, three waves without work), N = 33 (the last
+    strip holds one column) and skipped slots."""
+    E, S, K, N, T = 3, 4, 96, 33, 17
+    q, s, W = rand_mx(E, N, K, 3433)
+    g = torch.Generator().manual_seed(3433 + T)
+    x = (torch.randn((T, S, K), generator=g) * 0.5).to(dt)
+    bias = torch.randn((E, N), generator=g).to(dt).to(DEV)
+    idx = make_idx(T, S, E, 3433)
+    assert bool(((idx < 0) | (idx >= E)).any())
+    yref, a = aref.experts(x, idx, W, bias)
+    cq, cs, cf = ext().quantize_act(x.to(DEV).reshape(-1, K))
+    y = ext().gemm(cq, cs, cf, idx.to(DEV), q, s, bias, dtype=dt, form=0)
+    assert y.dtype == dt and y.shape == (T, S, N)
+    check(y, yref, a, K, dt, idx, E)
+
+
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("K", [ONE_K, ONE_K + 32])
 def test_decode_form_at_and_beyond_the_one_launch_k(K, dt):
     """K = 16384 is one launch (the row image fills its 12800 bytes of LDS); K = 16416 is the quantise launch and the routed kernel

@@ -172,7 +172,7 @@ KN = ((32, 1), (96, 3), (160, 16), (1024, 17), (4096, 130), (160, 257), (32, 130
 DECODE_M = (1, 5, 16, 17, 33, 64)
 PREFILL_M = (65, 130, 300)
 
-SHAPES = [(M, K, N) for M in DECODE_M + PREFILL_M for K, N in KN] + [(257, 160, 21846)]
+SHAPES = [(M, K, N) for M in DECODE_M + PREFILL_M for K, N in KN] + [(257, 160, 21846)] + [(33, 96, 130)]
 
 
 @pytest.mark.parametrize("dt", DTS)
