@@ -13,50 +13,26 @@ dequant_act are mxfp6_a6_linear_cuda's.  Nothing here synchronises with the host
 be captured in a graph."""
 import torch
 
-from bitorch_engine import _hip
+from bitorch_engine.extensions import _mx_scaled
 from bitorch_engine.extensions.mxfp4_experts_a8_cuda import _bias
 from bitorch_engine.extensions.mxfp4_experts_cuda import _shape, blk_exp, col_exp, dequant, grad_input, quantize  # noqa: F401
-from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned
 from bitorch_engine.extensions.mxfp6_a6_linear_cuda import dequant_act, quantize_act  # noqa: F401
+
+
+_LAYER = _mx_scaled.Experts("mx4a6_moe", "mxfp4 a6", 24, _shape, col_exp)
+_idx = _LAYER.idx
 
 
 def form(P: int, E: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
     """0 = routed decode form, 1 = grouped prefill form (bie_mx4a6_moe_form); P = the number of (token, slot) pairs."""
-    return int(_hip.lib().bie_mx4a6_moe_form(P, E, N, K, _hip._DT[dtype]))
-
-
-def _idx(idx):
-    if idx.dtype != torch.int32 or idx.dim() != 2:
-        raise RuntimeError(f"mxfp4 a6 experts: idx must be int32 [T, S] (got {idx.dtype} {tuple(idx.shape)})")
-    return idx.shape
+    return _LAYER.form(P, E, N, K, dtype)
 
 
 def forward(x: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor = None, e_col: torch.Tensor = None,
             form: int = -1) -> torch.Tensor:
     """x [T, K] or [T, S, K] (fp16 / bf16), idx int32 [T, S] -> y [T, S, N] in x's dtype: quantise the rows of x, then the contraction.
     form -1 = the plan.  e_col (col_exp(scales)) is computed here when it is not given."""
-    _hip.need_gpu(x, idx, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 a6 experts: dtype {x.dtype} is not supported (fp16 / bf16)")
-    E, N, K = _shape(qweight, scales)
-    T, S = _idx(idx)
-    if tuple(x.shape) not in ((T, K), (T, S, K)):
-        raise RuntimeError(f"mxfp4 a6 experts: x {tuple(x.shape)} does not match idx {tuple(idx.shape)} and K={K}")
-    y = torch.empty((T, S, N), dtype=x.dtype, device=x.device)
-    if T * S == 0:
-        return y
-    L = _hip.lib()
-    if form < 0:
-        form = int(L.bie_mx4a6_moe_form(T * S, E, N, K, _hip.dt(x)))
-    if e_col is None:
-        e_col = col_exp(scales)
-    x_per_pair = int(x.dim() == 3)
-    ws = torch.empty(int(L.bie_mx4a6_moe_workspace_bytes(T, S, E, K, x_per_pair, int(form))), dtype=torch.uint8, device=x.device)
-    bias = _bias(bias, E, N, x.dtype)
-    x, idx, qweight, scales, e_col = _aligned(x), idx.contiguous(), _aligned(qweight), scales.contiguous(), e_col.contiguous()  # held until queued
-    _hip.check(L.bie_mx4a6_moe_forward(_hip.ptr(x), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y),
-                                       _hip.ptr(ws), T, S, E, N, K, x_per_pair, _hip.dt(x), int(form), _hip.stream()), "bie_mx4a6_moe_forward")
-    return y
+    return _LAYER.forward(x, idx, qweight, scales, bias, e_col, form)
 
 
 def gemm(xq6: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor,
@@ -64,30 +40,4 @@ def gemm(xq6: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, idx: torch
     """The contraction from already-quantised activations: xq6 uint8 [R, 3K/4], xs uint8 [R, K/32], row_flag uint8 [R] with R = T (every
     slot of a token reads the token's row) or R = T * S (a row per pair, in pair order) -> y [T, S, N] in dtype.  Form 0 here is the
     routed kernel reading xq6 from memory."""
-    _hip.need_gpu(xq6, xs, row_flag, idx, qweight, scales, bias, e_col)
-    if dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 a6 experts gemm: dtype {dtype} is not supported (fp16 / bf16)")
-    E, N, K = _shape(qweight, scales)
-    T, S = _idx(idx)
-    R = xq6.shape[0]
-    if (xq6.dtype != torch.uint8 or xs.dtype != torch.uint8 or row_flag.dtype != torch.uint8 or tuple(xq6.shape) != (R, K // 32 * 24)
-            or tuple(xs.shape) != (R, K // 32) or tuple(row_flag.shape) != (R,) or R not in (T, T * S)):
-        raise RuntimeError(f"mxfp4 a6 experts gemm: xq6 {tuple(xq6.shape)} / xs {tuple(xs.shape)} / row_flag {tuple(row_flag.shape)} do not match "
-                           f"idx {tuple(idx.shape)} and K={K} (uint8 [R, 3K/4] / [R, K/32] / [R], T or T * S rows)")
-    y = torch.empty((T, S, N), dtype=dtype, device=xq6.device)
-    if T * S == 0:
-        return y
-    x_per_pair = int(R != T)  # S = 1: the two readings are the same rows
-    L = _hip.lib()
-    if form < 0:
-        form = int(L.bie_mx4a6_moe_form(T * S, E, N, K, _hip._DT[dtype]))
-    if e_col is None:
-        e_col = col_exp(scales)
-    ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(T * S, E)), dtype=torch.uint8, device=xq6.device) if form == 1 else None
-    bias = _bias(bias, E, N, dtype)
-    xq6, xs, row_flag, idx = _aligned(xq6), xs.contiguous(), row_flag.contiguous(), idx.contiguous()
-    qweight, scales, e_col = _aligned(qweight), scales.contiguous(), e_col.contiguous()
-    _hip.check(L.bie_mx4a6_moe_gemm(_hip.ptr(xq6), _hip.ptr(xs), _hip.ptr(row_flag), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col),
-                                    _hip.ptr(bias), _hip.ptr(y), _hip.ptr(ws), T, S, E, N, K, x_per_pair, _hip._DT[dtype], int(form), _hip.stream()),
-               "bie_mx4a6_moe_gemm")
-    return y
+    return _LAYER.gemm(xq6, xs, row_flag, idx, qweight, scales, bias, e_col, dtype, form)

@@ -14,6 +14,7 @@ one: the scale bytes are the same).  Nothing here synchronises with the host, so
 import torch
 
 from bitorch_engine import _hip
+from bitorch_engine.extensions import _mx_scaled
 from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, blk_exp, col_exp  # noqa: F401
 from bitorch_engine.extensions.mxfp4_a8_linear_cuda import _act_shape, _bias, dequant_act, quantize_act  # noqa: F401
 
@@ -48,56 +49,25 @@ def dequant(qweight: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = to
     return w
 
 
+_LAYER = _mx_scaled.Dense("mxfp6_a8", "mxfp6 a8", 32, _shape, col_exp, act_shape=_act_shape)
+
+
 def form(M: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
     """0 = decode form, 1 = prefill form (bie_mxfp6_a8_form)."""
-    return int(_hip.lib().bie_mxfp6_a8_form(M, N, K, _hip._DT[dtype]))
+    return _LAYER.form(M, N, K, dtype)
 
 
 def forward(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor = None, e_col: torch.Tensor = None,
             form: int = -1) -> torch.Tensor:
     """x [M, K] (fp16 / bf16) -> y [M, N] in x's dtype: quantise x, then the contraction.  form -1 = the plan.  e_col (col_exp(scales)) is
     computed here when it is not given."""
-    _hip.need_gpu(x, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 a8 linear: dtype {x.dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    if x.dim() != 2 or x.shape[1] != K:
-        raise RuntimeError(f"mxfp6 a8 linear: x {tuple(x.shape)} does not match K={K}")
-    M = x.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    if M == 0:
-        return y
-    L = _hip.lib()
-    if e_col is None:
-        e_col = col_exp(scales)
-    ws = torch.empty(int(L.bie_mxfp6_a8_workspace_bytes(M, N, K, int(form))), dtype=torch.uint8, device=x.device)
-    bias = _bias(bias, x.dtype)
-    x, qweight, scales = _aligned(x), _aligned(qweight), scales.contiguous()  # held until the launches are queued
-    _hip.check(L.bie_mxfp6_a8_linear_forward(_hip.ptr(x), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y), _hip.ptr(ws),
-                                             M, N, K, _hip.dt(x), int(form), _hip.stream()), "bie_mxfp6_a8_linear_forward")
-    return y
+    return _LAYER.forward(x, qweight, scales, bias, e_col, form)
 
 
 def gemm(xq: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor = None,
          e_col: torch.Tensor = None, dtype: torch.dtype = torch.float16, form: int = -1) -> torch.Tensor:
     """The contraction from already-quantised activations (xq uint8 [M, K], xs uint8 [M, K/32], row_flag uint8 [M]) -> y [M, N] in dtype."""
-    _hip.need_gpu(xq, xs, row_flag, qweight, scales, bias, e_col)
-    if dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 a8 gemm: dtype {dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    M = xq.shape[0]
-    if _act_shape(xq, xs) != (M, K) or row_flag.dtype != torch.uint8 or tuple(row_flag.shape) != (M,):
-        raise RuntimeError(f"mxfp6 a8 gemm: xq {tuple(xq.shape)} / xs {tuple(xs.shape)} / row_flag {tuple(row_flag.shape)} do not match K={K}")
-    y = torch.empty((M, N), dtype=dtype, device=xq.device)
-    if M == 0:
-        return y
-    if e_col is None:
-        e_col = col_exp(scales)
-    bias = _bias(bias, dtype)
-    xq, xs, row_flag, qweight, scales = _aligned(xq), xs.contiguous(), row_flag.contiguous(), _aligned(qweight), scales.contiguous()
-    _hip.check(_hip.lib().bie_mxfp6_a8_gemm(_hip.ptr(xq), _hip.ptr(xs), _hip.ptr(row_flag), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col),
-                                            _hip.ptr(bias), _hip.ptr(y), None, M, N, K, _hip._DT[dtype], int(form), _hip.stream()), "bie_mxfp6_a8_gemm")
-    return y
+    return _LAYER.gemm(xq, xs, row_flag, qweight, scales, bias, e_col, dtype, form)
 
 
 def grad_input(gy: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None) -> torch.Tensor:

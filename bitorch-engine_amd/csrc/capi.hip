@@ -1120,11 +1120,61 @@ static int check_mxa4(const char* what, long M, long N, long K, int dtype) {
     return BIE_OK;
 }
 
-static int check_mxa4_form(const char* what, long M, long N, long K, int dtype, int* form) {
+// One entry check for the six block-scaled dense layers (W4A4, W4A8, W6A8, W6A6, W4A6, W8A8; their host side is csrc/mx_scaled_launch.cuh).
+// A row names the layer's functions and what its messages call the quantised rows.
+struct mx_dense_entry {
+    int (*form)(long M, long N, long K, int dtype);
+    bool (*decode_ok)(long M);
+    size_t (*workspace_bytes)(long M, long K);
+    int (*forward)(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M, long N,
+                   long K, int dtype, int form, hipStream_t st);
+    int (*gemm)(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias,
+                void* y, long M, long N, long K, int dtype, int form, hipStream_t st);
+    const char* xq;
+};
+static const mx_dense_entry MX_W4A4 = {mxfp4_a4_form, mxfp4_a4_decode_ok, mxfp4_a4_workspace_bytes, mxfp4_a4_forward_launch, mxfp4_a4_gemm_launch, "xq"};
+static const mx_dense_entry MX_W4A8 = {mxfp4_a8_form, mxfp4_a8_decode_ok, mxfp4_a8_workspace_bytes, mxfp4_a8_forward_launch, mxfp4_a8_gemm_launch, "xq"};
+static const mx_dense_entry MX_W6A8 = {mxfp6_a8_form, mxfp6_a8_decode_ok, mxfp6_a8_workspace_bytes, mxfp6_a8_forward_launch, mxfp6_a8_gemm_launch, "xq"};
+static const mx_dense_entry MX_W6A6 = {mxfp6_a6_form, mxfp6_a6_decode_ok, mxfp6_a6_workspace_bytes, mxfp6_a6_forward_launch, mxfp6_a6_gemm_launch, "xq6"};
+static const mx_dense_entry MX_W4A6 = {mxfp4_a6_form, mxfp4_a6_decode_ok, mxfp4_a6_workspace_bytes, mxfp4_a6_forward_launch, mxfp4_a6_gemm_launch, "xq6"};
+static const mx_dense_entry MX_W8A8 = {mxfp8_a8_form, mxfp8_a8_decode_ok, mxfp4_a8_workspace_bytes, mxfp8_a8_forward_launch, mxfp8_a8_gemm_launch, "xq"};  // W4A8's layout
+
+// The shape and dtype limits (check_mxa4), then the form: -1 asks the layer's plan, and the decode form has a row bound.
+static int check_mx_dense(const mx_dense_entry& L, const char* what, long M, long N, long K, int dtype, int* form) {
+    int rc = check_mxa4(what, M, N, K, dtype);
+    if (rc) return rc;
     BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp4_a4_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_a4_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
+    if (*form < 0) *form = L.form(M, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || L.decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
     return BIE_OK;
+}
+
+static size_t mx_dense_workspace(const mx_dense_entry& L, long M, long N, long K, int form) {
+    (void)N; (void)form;  // one layout serves either form
+    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
+    return L.workspace_bytes(M, K);
+}
+
+static int mx_dense_forward(const mx_dense_entry& L, const char* what, const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                            const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mx_dense(L, what, M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", what);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "%s: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned", what);
+    return L.forward(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+}
+
+static int mx_dense_gemm(const mx_dense_entry& L, const char* what, const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight,
+                         const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form,
+                         void* stream) {
+    (void)workspace;  // neither form needs one beyond the quantised activations it is given
+    int rc = check_mx_dense(L, what, M, N, K, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", what);
+    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "%s: %s, qweight and y must be 16-byte aligned, bias 2-byte aligned", what, L.xq);
+    return L.gemm(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
 }
 
 int bie_mxfp4_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream) {
@@ -1137,45 +1187,19 @@ int bie_mxfp4_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row
 
 int bie_mxfp4_a4_form(long M, long N, long K, int dtype) { return mxfp4_a4_form(M, N, K, dtype); }
 
-size_t bie_mxfp4_a4_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp4_a4_workspace_bytes(M, K);
-}
+size_t bie_mxfp4_a4_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W4A4, M, N, K, form); }
 
 int bie_mxfp4_a4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                                 void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mxfp4_a4_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mxa4_form("bie_mxfp4_a4_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mxfp4_a4_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp4_a4_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a4_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W4A4, "bie_mxfp4_a4_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mxfp4_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mxfp4_a4_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mxa4_form("bie_mxfp4_a4_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mxfp4_a4_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp4_a4_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a4_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W4A4, "bie_mxfp4_a4_gemm", xq, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP4 W4A8 (MXFP8 activations).  Everything is checked here, before any device call; the shape limits are W4A4's (check_mxa4).
-static int check_mxa8_form(const char* what, long M, long N, long K, int dtype, int* form) {
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp4_a8_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_a8_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
-    return BIE_OK;
-}
-
 int bie_mxfp8_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream) {
     int rc = check_mxa4("bie_mxfp8_quantize_act", M, 1, K, dtype);
     if (rc) return rc;
@@ -1186,46 +1210,20 @@ int bie_mxfp8_quantize_act(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row
 
 int bie_mxfp4_a8_form(long M, long N, long K, int dtype) { return mxfp4_a8_form(M, N, K, dtype); }
 
-size_t bie_mxfp4_a8_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp4_a8_workspace_bytes(M, K);
-}
+size_t bie_mxfp4_a8_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W4A8, M, N, K, form); }
 
 int bie_mxfp4_a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                                 void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mxfp4_a8_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mxa8_form("bie_mxfp4_a8_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mxfp4_a8_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp4_a8_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a8_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W4A8, "bie_mxfp4_a8_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mxfp4_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mxfp4_a8_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mxa8_form("bie_mxfp4_a8_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mxfp4_a8_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp4_a8_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a8_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W4A8, "bie_mxfp4_a8_gemm", xq, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP6 W6A8 (MXFP6 weights, MXFP8 activations).  Everything is checked here, before any device call; the shape limits are W4A4's
 // (check_mx, check_mxa4).
-static int check_mx6a8_form(const char* what, long M, long N, long K, int dtype, int* form) {
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp6_a8_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp6_a8_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
-    return BIE_OK;
-}
-
 int bie_mxfp6_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream) {
     int rc = check_mx("bie_mxfp6_quantize", N, K);
     if (rc) return rc;
@@ -1246,46 +1244,20 @@ int bie_mxfp6_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, lo
 
 int bie_mxfp6_a8_form(long M, long N, long K, int dtype) { return mxfp6_a8_form(M, N, K, dtype); }
 
-size_t bie_mxfp6_a8_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp6_a8_workspace_bytes(M, K);
-}
+size_t bie_mxfp6_a8_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W6A8, M, N, K, form); }
 
 int bie_mxfp6_a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                                 void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mxfp6_a8_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx6a8_form("bie_mxfp6_a8_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mxfp6_a8_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp6_a8_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp6_a8_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W6A8, "bie_mxfp6_a8_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mxfp6_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mxfp6_a8_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx6a8_form("bie_mxfp6_a8_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mxfp6_a8_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp6_a8_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp6_a8_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W6A8, "bie_mxfp6_a8_gemm", xq, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP6 W6A6 (MXFP6 weights, MXFP6 activations).  Everything is checked here, before any device call; the shape limits are W4A4's
 // (check_mx, check_mxa4), the return codes the W6A8 entries'.
-static int check_mx6a6_form(const char* what, long M, long N, long K, int dtype, int* form) {
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp6_a6_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp6_a6_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
-    return BIE_OK;
-}
-
 int bie_mxfp6_quantize_act(const void* x, uint8_t* xq6, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, void* stream) {
     int rc = check_mxa4("bie_mxfp6_quantize_act", M, 1, K, dtype);
     if (rc) return rc;
@@ -1296,88 +1268,36 @@ int bie_mxfp6_quantize_act(const void* x, uint8_t* xq6, uint8_t* xs, uint8_t* ro
 
 int bie_mxfp6_a6_form(long M, long N, long K, int dtype) { return mxfp6_a6_form(M, N, K, dtype); }
 
-size_t bie_mxfp6_a6_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp6_a6_workspace_bytes(M, K);
-}
+size_t bie_mxfp6_a6_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W6A6, M, N, K, form); }
 
 int bie_mxfp6_a6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                                 void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mxfp6_a6_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx6a6_form("bie_mxfp6_a6_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mxfp6_a6_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp6_a6_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp6_a6_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W6A6, "bie_mxfp6_a6_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mxfp6_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                       const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mxfp6_a6_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx6a6_form("bie_mxfp6_a6_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq6 && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mxfp6_a6_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp6_a6_gemm: xq6, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp6_a6_gemm_launch(xq6, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W6A6, "bie_mxfp6_a6_gemm", xq6, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP4 W4A6 (MXFP4 weights, MXFP6 activations: bie_mxfp6_quantize_act's).  Everything is checked here, before any device call; the
 // shape limits are W4A4's (check_mx, check_mxa4), the return codes the W4A8 entries'.
-static int check_mx4a6_form(const char* what, long M, long N, long K, int dtype, int* form) {
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp4_a6_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_a6_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
-    return BIE_OK;
-}
-
 int bie_mx4a6_form(long M, long N, long K, int dtype) { return mxfp4_a6_form(M, N, K, dtype); }
 
-size_t bie_mx4a6_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp4_a6_workspace_bytes(M, K);
-}
+size_t bie_mx4a6_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W4A6, M, N, K, form); }
 
 int bie_mx4a6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                              void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mx4a6_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx4a6_form("bie_mx4a6_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mx4a6_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mx4a6_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a6_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W4A6, "bie_mx4a6_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mx4a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                    const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mx4a6_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx4a6_form("bie_mx4a6_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq6 && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mx4a6_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mx4a6_gemm: xq6, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp4_a6_gemm_launch(xq6, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W4A6, "bie_mx4a6_gemm", xq6, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP8 W8A8 (MXFP8 weights, MXFP8 activations: bie_mxfp8_quantize_act's).  Everything is checked here, before any device call; the
 // shape limits are W4A4's (check_mx, check_mxa4), the return codes the W4A8 entries'.
-static int check_mx8a8_form(const char* what, long M, long N, long K, int dtype, int* form) {
-    BIE_REQUIRE(*form >= -1 && *form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", what, *form);
-    if (*form < 0) *form = mxfp8_a8_form(M, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp8_a8_decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= 64 (M=%ld)", what, M);
-    return BIE_OK;
-}
-
 int bie_mx8_quantize(const void* w, uint8_t* qweight, uint8_t* scales, long N, long K, int dtype, void* stream) {
     int rc = check_mx("bie_mx8_quantize", N, K);
     if (rc) return rc;
@@ -1398,35 +1318,16 @@ int bie_mx8_dequant(const uint8_t* qweight, const uint8_t* scales, void* w, long
 
 int bie_mx8a8_form(long M, long N, long K, int dtype) { return mxfp8_a8_form(M, N, K, dtype); }
 
-size_t bie_mx8a8_workspace_bytes(long M, long N, long K, int form) {
-    (void)N; (void)form;
-    if (M <= 0 || M >= (1L << 31) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    return mxfp4_a8_workspace_bytes(M, K);
-}
+size_t bie_mx8a8_workspace_bytes(long M, long N, long K, int form) { return mx_dense_workspace(MX_W8A8, M, N, K, form); }
 
 int bie_mx8a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y,
                              void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mx8a8_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx8a8_form("bie_mx8a8_linear_forward", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(x && qweight && scales && e_col && y && workspace, BIE_ERR_INVALID_ARG, "bie_mx8a8_linear_forward: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(workspace, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mx8a8_linear_forward: x, qweight, y and workspace must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp8_a8_forward_launch(x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_forward(MX_W8A8, "bie_mx8a8_linear_forward", x, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 int bie_mx8a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                    const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
-    (void)workspace;  // neither form needs one beyond the quantised activations it is given
-    int rc = check_mxa4("bie_mx8a8_gemm", M, N, K, dtype);
-    if (rc) return rc;
-    rc = check_mx8a8_form("bie_mx8a8_gemm", M, N, K, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && qweight && scales && e_col && y, BIE_ERR_INVALID_ARG, "bie_mx8a8_gemm: NULL tensor pointer");
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(y, 16) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mx8a8_gemm: xq, qweight and y must be 16-byte aligned, bias 2-byte aligned");
-    return mxfp8_a8_gemm_launch(xq, xs, row_flag, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_dense_gemm(MX_W8A8, "bie_mx8a8_gemm", xq, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP6 weight-only (W6A16).  Everything is checked here, before any device call; the shape limits are the MXFP4 layer's.
@@ -1505,17 +1406,41 @@ int bie_mxfp6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qwei
     return mxfp6_moe_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
 }
 
-// ---- MXFP4 W4A4 mixture of experts.  Everything is checked here, before any device call.
-int bie_mxfp4_moe_a4_form(long P, long E, long N, long K, int dtype) { return mxfp4_moe_a4_form(P, E, N, K, dtype); }
+// ---- The block-scaled MX expert layers (W4A4, W4A8, W6A8, W6A6, W4A6; their host side is csrc/mx_scaled_launch.cuh): one entry check.
+// Everything is checked here, before any device call.  A row names the layer's functions, what its messages call the quantised rows, and
+// whether its column tiles are counted at 64 columns too (the layers that have a 128 x 64 tile).  The weight offsets of the MXFP6 layers
+// (up to E * N * K/32 * 24 bytes) are formed in 64 bits in the kernels.
+struct mx_grouped_entry {
+    int (*form)(long P, long E, long N, long K, int dtype);
+    bool (*decode_ok)(long P);
+    bool (*one_launch_ok)(long K);
+    size_t (*workspace_bytes)(long T, long S, long E, long K, int x_per_pair, int form);
+    int (*forward)(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace,
+                   long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
+    int (*gemm)(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
+                const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
+    const char* xq;
+    bool tiles64;
+};
+static const mx_grouped_entry MX_MOE_W4A4 = {mxfp4_moe_a4_form, mxfp4_moe_a4_decode_ok, mxfp4_moe_a4_one_launch_ok, mxfp4_moe_a4_workspace_bytes,
+                                             mxfp4_moe_a4_forward_launch, mxfp4_moe_a4_gemm_launch, "xq", false};
+static const mx_grouped_entry MX_MOE_W4A8 = {mxfp4_moe_a8_form, mxfp4_moe_a8_decode_ok, mxfp4_moe_a8_one_launch_ok, mxfp4_moe_a8_workspace_bytes,
+                                             mxfp4_moe_a8_forward_launch, mxfp4_moe_a8_gemm_launch, "xq", false};
+static const mx_grouped_entry MX_MOE_W6A8 = {mxfp6_moe_a8_form, mxfp6_moe_a8_decode_ok, mxfp6_moe_a8_one_launch_ok, mxfp6_moe_a8_workspace_bytes,
+                                             mxfp6_moe_a8_forward_launch, mxfp6_moe_a8_gemm_launch, "xq", true};
+static const mx_grouped_entry MX_MOE_W6A6 = {mxfp6_moe_a6_form, mxfp6_moe_a6_decode_ok, mxfp6_moe_a6_one_launch_ok, mxfp6_moe_a6_workspace_bytes,
+                                             mxfp6_moe_a6_forward_launch, mxfp6_moe_a6_gemm_launch, "xq6", true};
+static const mx_grouped_entry MX_MOE_W4A6 = {mxfp4_moe_a6_form, mxfp4_moe_a6_decode_ok, mxfp4_moe_a6_one_launch_ok, mxfp4_moe_a6_workspace_bytes,
+                                             mxfp4_moe_a6_forward_launch, mxfp4_moe_a6_gemm_launch, "xq6", true};
 
-size_t bie_mxfp4_moe_a4_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+static size_t mx_grouped_workspace(const mx_grouped_entry& L, long T, long S, long E, long K, int x_per_pair, int form) {
     if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
     if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
-    if (form == 0 && !mxfp4_moe_a4_decode_ok(T * S)) return 0;
-    return mxfp4_moe_a4_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
+    if (form == 0 && !L.decode_ok(T * S)) return 0;
+    return L.workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
 }
 
-// The shape limits shared by the W4A4 and W4A8 expert entries.
+// The shape limits shared by the expert entries.
 static int check_mx_moe_act(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form) {
     int rc = check_mx(fn, N, K);
     if (rc) return rc;
@@ -1532,244 +1457,133 @@ static int check_mx_moe_act(const char* fn, long T, long S, long E, long N, long
     return BIE_OK;
 }
 
-static int check_mx_moe_a4(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
+// The shape limits, then the form: -1 asks the layer's plan, and the decode form has a pair bound.
+static int check_mx_grouped(const mx_grouped_entry& L, const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
     const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
     if (rc) return rc;
     const long P = T * S;
-    if (*form < 0) *form = mxfp4_moe_a4_form(P, E, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_moe_a4_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
+    BIE_REQUIRE(!L.tiles64 || (P / 128 + E + 1) * ((N + 63) / 64) < (1L << 31), BIE_ERR_UNSUPPORTED,
+                "%s: P * N = %ld beyond the layer's range (the grid of 128 x 64 tiles)", fn, P * N);
+    if (*form < 0) *form = L.form(P, E, N, K, dtype);
+    BIE_REQUIRE(*form == 1 || L.decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
     return BIE_OK;
 }
 
-int bie_mxfp4_moe_a4_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
-                             void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp4_moe_a4_forward";
-    int rc = check_mx_moe_a4(fn, T, S, E, N, K, x_per_pair, dtype, &form);
+static int mx_grouped_forward(const mx_grouped_entry& L, const char* fn, const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                              const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                              int dtype, int form, void* stream) {
+    int rc = check_mx_grouped(L, fn, T, S, E, N, K, x_per_pair, dtype, &form);
     if (rc) return rc;
-    const bool need_ws = form == 1 || !mxfp4_moe_a4_one_launch_ok(K);
+    const bool need_ws = form == 1 || !L.one_launch_ok(K);
     BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
                 "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
     BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
                     (!need_ws || !misaligned(workspace, 16)),
                 BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a4_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return L.forward(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+}
+
+static int mx_grouped_gemm(const mx_grouped_entry& L, const char* fn, const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx,
+                           const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S,
+                           long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    int rc = check_mx_grouped(L, fn, T, S, E, N, K, x_per_pair, dtype, &form);
+    if (rc) return rc;
+    BIE_REQUIRE(xq && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
+                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
+    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
+                    (form == 0 || !misaligned(workspace, 16)),
+                BIE_ERR_INVALID_ARG, "%s: %s, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn, L.xq);
+    return L.gemm(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+}
+
+int bie_mxfp4_moe_a4_form(long P, long E, long N, long K, int dtype) { return MX_MOE_W4A4.form(P, E, N, K, dtype); }
+
+size_t bie_mxfp4_moe_a4_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
+    return mx_grouped_workspace(MX_MOE_W4A4, T, S, E, K, x_per_pair, form);
+}
+
+int bie_mxfp4_moe_a4_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                             void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    return mx_grouped_forward(MX_MOE_W4A4, "bie_mxfp4_moe_a4_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 int bie_mxfp4_moe_a4_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp4_moe_a4_gemm";
-    int rc = check_mx_moe_a4(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: xq, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a4_gemm_launch(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
-                                    as_stream(stream));
+    return mx_grouped_gemm(MX_MOE_W4A4, "bie_mxfp4_moe_a4_gemm", xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype,
+                           form, stream);
 }
 
-// ---- MXFP4 W4A8 mixture of experts.  Everything is checked here, before any device call; the shape limits are the W4A4 entries' (check_mx_moe_act).
-int bie_mxfp4_moe_a8_form(long P, long E, long N, long K, int dtype) { return mxfp4_moe_a8_form(P, E, N, K, dtype); }
+int bie_mxfp4_moe_a8_form(long P, long E, long N, long K, int dtype) { return MX_MOE_W4A8.form(P, E, N, K, dtype); }
 
 size_t bie_mxfp4_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
-    if (form == 0 && !mxfp4_moe_a8_decode_ok(T * S)) return 0;
-    return mxfp4_moe_a8_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
-}
-
-static int check_mx_moe_a8(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
-    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
-    if (rc) return rc;
-    const long P = T * S;
-    if (*form < 0) *form = mxfp4_moe_a8_form(P, E, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_moe_a8_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
-    return BIE_OK;
+    return mx_grouped_workspace(MX_MOE_W4A8, T, S, E, K, x_per_pair, form);
 }
 
 int bie_mxfp4_moe_a8_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                              void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp4_moe_a8_forward";
-    int rc = check_mx_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    const bool need_ws = form == 1 || !mxfp4_moe_a8_one_launch_ok(K);
-    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (!need_ws || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a8_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return mx_grouped_forward(MX_MOE_W4A8, "bie_mxfp4_moe_a8_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 int bie_mxfp4_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp4_moe_a8_gemm";
-    int rc = check_mx_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: xq, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a8_gemm_launch(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
-                                    as_stream(stream));
+    return mx_grouped_gemm(MX_MOE_W4A8, "bie_mxfp4_moe_a8_gemm", xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype,
+                           form, stream);
 }
 
-// ---- MXFP6 W6A8 mixture of experts.  Everything is checked here, before any device call; the shape limits are the W4A4 / W4A8 entries'
-// (check_mx_moe_act), with the column tiles counted at this layer's 64 columns.  The weight offsets (up to E * N * K/32 * 24 bytes) are
-// formed in 64 bits in the kernels.
-int bie_mxfp6_moe_a8_form(long P, long E, long N, long K, int dtype) { return mxfp6_moe_a8_form(P, E, N, K, dtype); }
+int bie_mxfp6_moe_a8_form(long P, long E, long N, long K, int dtype) { return MX_MOE_W6A8.form(P, E, N, K, dtype); }
 
 size_t bie_mxfp6_moe_a8_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
-    if (form == 0 && !mxfp6_moe_a8_decode_ok(T * S)) return 0;
-    return mxfp6_moe_a8_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
-}
-
-static int check_mx6_moe_a8(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
-    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
-    if (rc) return rc;
-    const long P = T * S;
-    BIE_REQUIRE((P / 128 + E + 1) * ((N + 63) / 64) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: P * N = %ld beyond the layer's range (the grid of 128 x 64 tiles)",
-                fn, P * N);
-    if (*form < 0) *form = mxfp6_moe_a8_form(P, E, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp6_moe_a8_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
-    return BIE_OK;
+    return mx_grouped_workspace(MX_MOE_W6A8, T, S, E, K, x_per_pair, form);
 }
 
 int bie_mxfp6_moe_a8_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                              void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp6_moe_a8_forward";
-    int rc = check_mx6_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    const bool need_ws = form == 1 || !mxfp6_moe_a8_one_launch_ok(K);
-    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (!need_ws || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp6_moe_a8_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return mx_grouped_forward(MX_MOE_W6A8, "bie_mxfp6_moe_a8_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 int bie_mxfp6_moe_a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp6_moe_a8_gemm";
-    int rc = check_mx6_moe_a8(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
-    BIE_REQUIRE(!misaligned(xq, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: xq, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp6_moe_a8_gemm_launch(xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
-                                    as_stream(stream));
+    return mx_grouped_gemm(MX_MOE_W6A8, "bie_mxfp6_moe_a8_gemm", xq, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype,
+                           form, stream);
 }
 
-// ---- MXFP6 W6A6 mixture of experts.  Everything is checked here, before any device call; the checks are the W6A8 expert entries'
-// (the column tiles are counted at 64 columns, the narrower of this layer's two tile widths).
-int bie_mxfp6_moe_a6_form(long P, long E, long N, long K, int dtype) { return mxfp6_moe_a6_form(P, E, N, K, dtype); }
+int bie_mxfp6_moe_a6_form(long P, long E, long N, long K, int dtype) { return MX_MOE_W6A6.form(P, E, N, K, dtype); }
 
 size_t bie_mxfp6_moe_a6_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
-    if (form == 0 && !mxfp6_moe_a6_decode_ok(T * S)) return 0;
-    return mxfp6_moe_a6_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
-}
-
-static int check_mx6_moe_a6(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
-    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
-    if (rc) return rc;
-    const long P = T * S;
-    BIE_REQUIRE((P / 128 + E + 1) * ((N + 63) / 64) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: P * N = %ld beyond the layer's range (the grid of 128 x 64 tiles)",
-                fn, P * N);
-    if (*form < 0) *form = mxfp6_moe_a6_form(P, E, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp6_moe_a6_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
-    return BIE_OK;
+    return mx_grouped_workspace(MX_MOE_W6A6, T, S, E, K, x_per_pair, form);
 }
 
 int bie_mxfp6_moe_a6_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                              void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp6_moe_a6_forward";
-    int rc = check_mx6_moe_a6(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    const bool need_ws = form == 1 || !mxfp6_moe_a6_one_launch_ok(K);
-    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (!need_ws || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp6_moe_a6_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return mx_grouped_forward(MX_MOE_W6A6, "bie_mxfp6_moe_a6_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 int bie_mxfp6_moe_a6_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
                           const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                           int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp6_moe_a6_gemm";
-    int rc = check_mx6_moe_a6(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq6 && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
-    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: xq6, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp6_moe_a6_gemm_launch(xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
-                                    as_stream(stream));
+    return mx_grouped_gemm(MX_MOE_W6A6, "bie_mxfp6_moe_a6_gemm", xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype,
+                           form, stream);
 }
 
-// ---- MXFP4 W4A6 mixture of experts.  Everything is checked here, before any device call; the checks are the W6A6 expert entries'
-// (check_mx_moe_act, and the column tiles counted at 64 columns, the narrower of this layer's two tile widths).
-int bie_mx4a6_moe_form(long P, long E, long N, long K, int dtype) { return mxfp4_moe_a6_form(P, E, N, K, dtype); }
+int bie_mx4a6_moe_form(long P, long E, long N, long K, int dtype) { return MX_MOE_W4A6.form(P, E, N, K, dtype); }
 
 size_t bie_mx4a6_moe_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    if (T < 1 || T > (1L << 22) || S < 1 || S > 32 || !mx_moe_pairs_ok(T * S, E) || K < 32 || K % 32 || K > (1L << 20)) return 0;
-    if ((x_per_pair != 0 && x_per_pair != 1) || form < -1 || form > 1) return 0;
-    if (form == 0 && !mxfp4_moe_a6_decode_ok(T * S)) return 0;
-    return mxfp4_moe_a6_workspace_bytes(T, S, E, K, x_per_pair, form < 0 ? 1 : form);  // -1: the larger layout, which serves either form
-}
-
-static int check_mx4a6_moe(const char* fn, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int* form) {
-    const int rc = check_mx_moe_act(fn, T, S, E, N, K, x_per_pair, dtype, *form);
-    if (rc) return rc;
-    const long P = T * S;
-    BIE_REQUIRE((P / 128 + E + 1) * ((N + 63) / 64) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: P * N = %ld beyond the layer's range (the grid of 128 x 64 tiles)",
-                fn, P * N);
-    if (*form < 0) *form = mxfp4_moe_a6_form(P, E, N, K, dtype);
-    BIE_REQUIRE(*form == 1 || mxfp4_moe_a6_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
-    return BIE_OK;
+    return mx_grouped_workspace(MX_MOE_W4A6, T, S, E, K, x_per_pair, form);
 }
 
 int bie_mx4a6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                           void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mx4a6_moe_forward";
-    int rc = check_mx4a6_moe(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    const bool need_ws = form == 1 || !mxfp4_moe_a6_one_launch_ok(K);
-    BIE_REQUIRE(x && idx && qweight && scales && e_col && y && (!need_ws || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (only the one-launch decode form takes no workspace)", fn);
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (!need_ws || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: x, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a6_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return mx_grouped_forward(MX_MOE_W4A6, "bie_mx4a6_moe_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 int bie_mx4a6_moe_gemm(const uint8_t* xq6, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
                        const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                        int dtype, int form, void* stream) {
-    const char* fn = "bie_mx4a6_moe_gemm";
-    int rc = check_mx4a6_moe(fn, T, S, E, N, K, x_per_pair, dtype, &form);
-    if (rc) return rc;
-    BIE_REQUIRE(xq6 && xs && row_flag && idx && qweight && scales && e_col && y && (form == 0 || workspace), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs the routing workspace)", fn);
-    BIE_REQUIRE(!misaligned(xq6, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 16) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: xq6, qweight, y and workspace must be 16-byte aligned, idx 4-byte, bias 2-byte aligned", fn);
-    return mxfp4_moe_a6_gemm_launch(xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form,
-                                    as_stream(stream));
+    return mx_grouped_gemm(MX_MOE_W4A6, "bie_mx4a6_moe_gemm", xq6, xs, row_flag, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype,
+                           form, stream);
 }
 
 // ---- MXFP4 input gradient.  Everything is checked here, before any device call.

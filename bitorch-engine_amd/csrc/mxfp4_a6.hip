@@ -24,12 +24,11 @@
 // mx_scaled_decode_rows (FP4 x FP6) of mx_scaled_decode.cuh; a lane's weight fragment is one non-temporal 16-byte load and its x
 // fragment its block's 24 bytes in three 8-byte loads.  Prefill form (mx4a6_gemm_kernel): mx_scaled_gemm_tile (FP4 x FP6) of mx_scaled_tile.cuh.
 #include "mxfp6_common.cuh"
+#include "mx_scaled_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-int mxfp6_a6_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);  // mxfp6_a6.hip
 
 // ---- decode form ------------------------------------------------------------------------------------------------------------------------
 // A workgroup per 16 output columns, M <= 16 G rows (mx_scaled_decode_rows).
@@ -62,66 +61,28 @@ __global__ __launch_bounds__(256) void mx4a6_gemm_kernel(const uint8_t* __restri
 constexpr int A46_DECODE_ROWS = 64;
 constexpr int A46_PLAN_ROWS = 64;
 
-bool mxfp4_a6_decode_ok(long M) { return M >= 1 && M <= A46_DECODE_ROWS; }
+struct mx4a6_layer {
+    using act = mx_act_fp6;  // the W6A6 layer's quantiser and workspace layout
+    static constexpr const char* form_knob = "BIE_MXFP4_A6_FORM";
+    static constexpr int decode_rows = A46_DECODE_ROWS, plan_rows = A46_PLAN_ROWS;
+    static constexpr const char* decode_name = "mx4a6_decode_kernel";
+    static constexpr const char* gemm_name = "mx4a6_gemm_kernel";
+    template <int DT, int G> static constexpr auto decode() { return mx4a6_decode_kernel<DT, G>; }
+    template <int DT, int W> static constexpr auto gemm() { return mx4a6_gemm_kernel<DT, W, W>; }
+};
 
-int mxfp4_a6_form(long M, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP4_A6_FORM", -1);
-    if (f == 0 && M <= A46_DECODE_ROWS) return 0;
-    if (f == 1) return 1;
-    return M <= A46_PLAN_ROWS ? 0 : 1;
-}
-
-// Workspace of bie_mx4a6_linear_forward: xq6 [M, 3K/4] (16-byte aligned), xs [M, K/32], row_flag [M]: the W6A6 layer's layout
-static size_t a46_xs_offset(long M, long K) { return (size_t)(M * (K / 32) * MX6_BLOCK_BYTES); }
-static size_t a46_flag_offset(long M, long K) { return a46_xs_offset(M, K) + (size_t)(M * (K / 32)); }
-size_t mxfp4_a6_workspace_bytes(long M, long K) { return (a46_flag_offset(M, K) + (size_t)M + 15) / 16 * 16; }
-
-template <int DT, int WM, int WN>
-static void a46_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const int tn = cdiv(N, 64 * WN);
-    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
-    hipLaunchKernelGGL((mx4a6_gemm_kernel<DT, WM, WN>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
-}
-
-template <int DT>
-static void a46_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                               const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    // 128 x 128 tiles where they give every CU of the card (256) at least two workgroups, else 64 x 64 tiles, as in the W4A8 launcher
-    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) a46_gemm_launch_t<DT, 2, 2>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-    else a46_gemm_launch_t<DT, 1, 1>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-}
-
-template <int DT>
-static void a46_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                                 const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const dim3 grid((unsigned)cdiv(N, 16));
-    if (M <= 16) hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else if (M <= 32) hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else hipLaunchKernelGGL((mx4a6_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-}
+bool mxfp4_a6_decode_ok(long M) { return mx_dense_decode_ok<mx4a6_layer>(M); }
+int mxfp4_a6_form(long M, long N, long K, int dtype) { (void)N; (void)K; (void)dtype; return mx_dense_form<mx4a6_layer>(M); }
+size_t mxfp4_a6_workspace_bytes(long M, long K) { return mx_dense_workspace_bytes<mx4a6_layer>(M, K); }
 
 int mxfp4_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
                          const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
-    if (form == 0) {
-        if (dtype == BIE_F16) a46_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        else a46_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        return check_launch("mx4a6_decode_kernel");
-    }
-    if (dtype == BIE_F16) a46_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    else a46_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    return check_launch("mx4a6_gemm_kernel");
+    return mx_dense_gemm_launch<mx4a6_layer>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
 }
 
 int mxfp4_a6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st) {
-    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* xs = xq + a46_xs_offset(M, K);
-    uint8_t* rf = xq + a46_flag_offset(M, K);
-    const int rc = mxfp6_a6_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
-    if (rc) return rc;
-    return mxfp4_a6_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+    return mx_dense_forward_launch<mx4a6_layer>(x, qw, sc, ecol, bias, y, workspace, M, N, K, dtype, form, st);
 }
 
 }  // namespace bie

@@ -22,16 +22,11 @@
 // pieces of codes, whole scale bytes) and reads weights from (long)e * N; rows past the segment enter as zero codes under scale code
 // 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the skipped bin run no K loop and store zeros.
 #include "mxfp4_a4_common.cuh"
+#include "mx_scaled_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-// mxfp4_a4.hip, mxfp4_moe.hip
-int mxfp4_a4_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
-size_t mxfp4_moe_workspace_bytes(long P, long E);
-long mxfp4_moe_max_tiles(long P, long E);
-int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
 
 // ---- routed decode form -------------------------------------------------------------------------------------------------------------------
 // The largest K of the one-launch form: a row's image in LDS is K / 2 bytes of codes and K / 32 scale bytes (17408 bytes at the bound).
@@ -172,84 +167,37 @@ __global__ __launch_bounds__(256) void mxma4_gemm_kernel(const uint8_t* __restri
 constexpr int MXMA4_PLAN_PAIRS = 32, MXMA4_PLAN_PAIRS_SPARSE = 64;
 constexpr int MXMA4_STRIP = 1;  // C16 of the decode form: strips of 16 columns (BIE_MXFP4_MOE_A4_STRIP = 1 / 2 / 4 under BIE_TUNING)
 
-bool mxfp4_moe_a4_decode_ok(long P) { return P >= 1 && P <= MXMA4_DECODE_PAIRS; }
-bool mxfp4_moe_a4_one_launch_ok(long K) { return K <= MXMA4_ONE_K; }
+// Workspace of bie_mxfp4_moe_a4_forward: xq [R, K/2], xs [R, K/32], row_flag [R], then the routing region (mx_scaled_launch.cuh)
+struct mxma4_layer {
+    using act = mx_act_fp4;
+    static constexpr const char* form_knob = "BIE_MXFP4_MOE_A4_FORM";
+    static constexpr const char* strip_knob = "BIE_MXFP4_MOE_A4_STRIP";
+    static constexpr const char* wn_knob = nullptr;
+    static constexpr int one_k = MXMA4_ONE_K, decode_pairs = MXMA4_DECODE_PAIRS;
+    static constexpr int plan_pairs = MXMA4_PLAN_PAIRS, plan_pairs_sparse = MXMA4_PLAN_PAIRS_SPARSE, plan_sparse_mul = 2;
+    static constexpr int strip = MXMA4_STRIP, wn = MXMA4_W;
+    static constexpr const char* decode_name = "mxma4_decode_kernel";
+    static constexpr const char* gemm_name = "mxma4_gemm_kernel";
+    template <int DT, int C16, bool FUSED> static constexpr auto decode() { return mxma4_decode_kernel<DT, C16, FUSED>; }
+    template <int DT, int WN> static constexpr auto gemm() { return mxma4_gemm_kernel<DT>; }
+};
 
-int mxfp4_moe_a4_form(long P, long E, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP4_MOE_A4_FORM", -1);
-    if (f == 0 && P <= MXMA4_DECODE_PAIRS) return 0;
-    if (f == 1) return 1;
-    return (P <= MXMA4_PLAN_PAIRS || (P <= MXMA4_PLAN_PAIRS_SPARSE && 2 * P <= E)) ? 0 : 1;
-}
-
-// Workspace of bie_mxfp4_moe_a4_forward, every region 16-byte aligned: xq [R, K/2], xs [R, K/32], row_flag [R] for the R stored rows of
-// x (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip.
-static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
-static long a4m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
-static size_t a4m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)(K / 2)); }
-static size_t a4m_flag_offset(long R, long K) { return a4m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
-static size_t a4m_route_offset(long R, long K) { return a4m_flag_offset(R, K) + al16((size_t)R); }
-
+bool mxfp4_moe_a4_decode_ok(long P) { return mx_grouped_decode_ok<mxma4_layer>(P); }
+bool mxfp4_moe_a4_one_launch_ok(long K) { return mx_grouped_one_launch_ok<mxma4_layer>(K); }
+int mxfp4_moe_a4_form(long P, long E, long N, long K, int dtype) { (void)N; (void)K; (void)dtype; return mx_grouped_form<mxma4_layer>(P, E); }
 size_t mxfp4_moe_a4_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    return a4m_route_offset(a4m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+    return mx_grouped_workspace_bytes<mxma4_layer>(T, S, E, K, x_per_pair, form);
 }
 
-template <int DT, int C16, bool FUSED>
-static void a4m_decode_launch_t(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
-                                const uint8_t* ecol, const void* bias, void* y, long P, int S, int E, int N, int K, int xpp, hipStream_t st) {
-    const dim3 grid((unsigned)cdivl(N, 16 * C16), (unsigned)P);
-    hipLaunchKernelGGL((mxma4_decode_kernel<DT, C16, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, S, E, N, K, xpp);
-}
-
-template <int DT, bool FUSED>
-static int a4m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
-                             const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
-    const int strip = BIE_KNOB("BIE_MXFP4_MOE_A4_STRIP", MXMA4_STRIP);
-    if (strip >= 4) a4m_decode_launch_t<DT, 4, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
-    else if (strip >= 2) a4m_decode_launch_t<DT, 2, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
-    else a4m_decode_launch_t<DT, 1, FUSED>(xin, xs, rf, idx, qw, sc, ecol, bias, y, P, (int)S, (int)E, (int)N, (int)K, xpp, st);
-    return check_launch("mxma4_decode_kernel");
-}
-
-// The contraction from quantised activations.  form 0: the routed kernel reading xq from memory (no workspace); form 1: routing into the
-// workspace (the routing region alone), then the grouped GEMM.
 int mxfp4_moe_a4_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
                              const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                              int dtype, int form, hipStream_t st) {
-    const long P = T * S;
-    if (form == 0) {
-        if (dtype == BIE_F16) return a4m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-        return a4m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-    }
-    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
-    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * MXMA4_W)));
-    if (dtype == BIE_F16)
-        hipLaunchKernelGGL(mxma4_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
-                           x_per_pair, max_tiles);
-    else
-        hipLaunchKernelGGL(mxma4_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xq, xs, row_flag, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K,
-                           x_per_pair, max_tiles);
-    return check_launch("mxma4_gemm_kernel");
+    return mx_grouped_gemm_launch<mxma4_layer>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
-// The whole layer from x.  form 0 with K <= MXMA4_ONE_K: one launch, the workspace is not touched.
 int mxfp4_moe_a4_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                                 void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
-    const long P = T * S, R = a4m_rows(T, S, x_per_pair);
-    if (form == 0 && K <= MXMA4_ONE_K) {
-        if (dtype == BIE_F16) return a4m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-        return a4m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-    }
-    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* xs = xq + a4m_xs_offset(R, K);
-    uint8_t* rf = xq + a4m_flag_offset(R, K);
-    const int rc = mxfp4_a4_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
-    if (rc) return rc;
-    return mxfp4_moe_a4_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a4m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+    return mx_grouped_forward_launch<mxma4_layer>(x, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
 }  // namespace bie

@@ -27,16 +27,11 @@
 // segment enter as zero codes under scale code 127 and are not stored; the epilogue scatters row r to y[pair r].  The tiles of the
 // skipped bin run no K loop and store zeros.
 #include "mxfp6_common.cuh"
+#include "mx_scaled_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-// mxfp6_a6.hip, mxfp4_moe.hip
-int mxfp6_a6_quantize_launch(const void* x, uint8_t* xq, uint8_t* xs, uint8_t* row_flag, long M, long K, int dtype, hipStream_t st);
-size_t mxfp4_moe_workspace_bytes(long P, long E);
-long mxfp4_moe_max_tiles(long P, long E);
-int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
 
 // ---- routed decode form -------------------------------------------------------------------------------------------------------------------
 // The largest K of the one-launch form, the sibling expert kernels' bound.  A row's image in LDS is 3K/4 code bytes and K/32 scale
@@ -103,85 +98,37 @@ constexpr int MX4M6_STRIP = 1;  // C16 of the decode form
 // not tried.
 constexpr int MX4M6_WN = 2;
 
-bool mxfp4_moe_a6_decode_ok(long P) { return P >= 1 && P <= MX4M6_DECODE_PAIRS; }
-bool mxfp4_moe_a6_one_launch_ok(long K) { return K <= MX4M6_ONE_K; }
+// Workspace of bie_mx4a6_moe_forward, the W6A6 expert layer's layout: xq6 [R, 3K/4], xs [R, K/32], row_flag [R], then the routing region (mx_scaled_launch.cuh)
+struct mx4m6_layer {
+    using act = mx_act_fp6;
+    static constexpr const char* form_knob = "BIE_MXFP4_MOE_A6_FORM";
+    static constexpr const char* strip_knob = nullptr;
+    static constexpr const char* wn_knob = "BIE_MXFP4_MOE_A6_WN";
+    static constexpr int one_k = MX4M6_ONE_K, decode_pairs = MX4M6_DECODE_PAIRS;
+    static constexpr int plan_pairs = MX4M6_PLAN_PAIRS, plan_pairs_sparse = MX4M6_PLAN_PAIRS_SPARSE, plan_sparse_mul = 1;
+    static constexpr int strip = MX4M6_STRIP, wn = MX4M6_WN;
+    static constexpr const char* decode_name = "mx4m6_decode_kernel";
+    static constexpr const char* gemm_name = "mx4m6_gemm_kernel";
+    template <int DT, int C16, bool FUSED> static constexpr auto decode() { return mx4m6_decode_kernel<DT, C16, FUSED>; }
+    template <int DT, int WN> static constexpr auto gemm() { return mx4m6_gemm_kernel<DT, WN>; }
+};
 
-int mxfp4_moe_a6_form(long P, long E, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP4_MOE_A6_FORM", -1);
-    if (f == 0 && P <= MX4M6_DECODE_PAIRS) return 0;
-    if (f == 1) return 1;
-    return (P <= MX4M6_PLAN_PAIRS || (P <= MX4M6_PLAN_PAIRS_SPARSE && P <= E)) ? 0 : 1;
-}
-
-// Workspace of bie_mx4a6_moe_forward, the W6A6 expert layer's layout: xq6 [R, 3K/4], xs [R, K/32], row_flag [R] for the R stored rows
-// of x (T, or P with x_per_pair), then for the grouped form the routing region of mxfp4_moe.hip; every region 16-byte aligned.
-static size_t al16(size_t v) { return (v + 15) / 16 * 16; }
-static long a46m_rows(long T, long S, int x_per_pair) { return x_per_pair ? T * S : T; }
-static size_t a46m_xs_offset(long R, long K) { return al16((size_t)R * (size_t)(K / 32) * MX6_BLOCK_BYTES); }
-static size_t a46m_flag_offset(long R, long K) { return a46m_xs_offset(R, K) + al16((size_t)R * (size_t)(K / 32)); }
-static size_t a46m_route_offset(long R, long K) { return a46m_flag_offset(R, K) + al16((size_t)R); }
-
+bool mxfp4_moe_a6_decode_ok(long P) { return mx_grouped_decode_ok<mx4m6_layer>(P); }
+bool mxfp4_moe_a6_one_launch_ok(long K) { return mx_grouped_one_launch_ok<mx4m6_layer>(K); }
+int mxfp4_moe_a6_form(long P, long E, long N, long K, int dtype) { (void)N; (void)K; (void)dtype; return mx_grouped_form<mx4m6_layer>(P, E); }
 size_t mxfp4_moe_a6_workspace_bytes(long T, long S, long E, long K, int x_per_pair, int form) {
-    return a46m_route_offset(a46m_rows(T, S, x_per_pair), K) + (form == 1 ? mxfp4_moe_workspace_bytes(T * S, E) : 0);
+    return mx_grouped_workspace_bytes<mx4m6_layer>(T, S, E, K, x_per_pair, form);
 }
 
-template <int DT, bool FUSED>
-static int a46m_decode_launch(const void* xin, const uint8_t* xs, const uint8_t* rf, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
-                              const uint8_t* ecol, const void* bias, void* y, long P, long S, long E, long N, long K, int xpp, hipStream_t st) {
-    const dim3 grid((unsigned)cdivl(N, 16 * MX4M6_STRIP), (unsigned)P);
-    hipLaunchKernelGGL((mx4m6_decode_kernel<DT, MX4M6_STRIP, FUSED>), grid, dim3(256), 0, st, xin, xs, rf, idx, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N,
-                       (int)K, xpp);
-    return check_launch("mx4m6_decode_kernel");
-}
-
-template <int DT, int WN>
-static void a46m_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const int32_t* ws, const uint8_t* qw, const uint8_t* sc,
-                               const uint8_t* ecol, const void* bias, void* y, long S, long E, long N, long K, int xpp, int max_tiles, hipStream_t st) {
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, 64 * WN)));
-    hipLaunchKernelGGL((mx4m6_gemm_kernel<DT, WN>), grid, dim3(256), 0, st, xq, xs, rf, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, xpp,
-                       max_tiles);
-}
-
-// The contraction from quantised activations.  form 0: the routed kernel reading xq6 from memory (no workspace); form 1: routing into the
-// workspace (the routing region alone), then the grouped GEMM.
 int mxfp4_moe_a6_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const int32_t* idx, const uint8_t* qw, const uint8_t* sc,
                              const uint8_t* ecol, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
                              int dtype, int form, hipStream_t st) {
-    const long P = T * S;
-    if (form == 0) {
-        if (dtype == BIE_F16) return a46m_decode_launch<BIE_F16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-        return a46m_decode_launch<BIE_BF16, false>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-    }
-    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
-    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
-    const bool wide = BIE_KNOB("BIE_MXFP4_MOE_A6_WN", MX4M6_WN) >= 2;
-    if (dtype == BIE_F16) {
-        if (wide) a46m_gemm_launch_t<BIE_F16, 2>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
-        else a46m_gemm_launch_t<BIE_F16, 1>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
-    } else {
-        if (wide) a46m_gemm_launch_t<BIE_BF16, 2>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
-        else a46m_gemm_launch_t<BIE_BF16, 1>(xq, xs, row_flag, ws, qw, sc, ecol, bias, y, S, E, N, K, x_per_pair, max_tiles, st);
-    }
-    return check_launch("mx4m6_gemm_kernel");
+    return mx_grouped_gemm_launch<mx4m6_layer>(xq, xs, row_flag, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
-// The whole layer from x.  form 0 with K <= MX4M6_ONE_K: one launch, the workspace is not touched.
 int mxfp4_moe_a6_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                                 void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
-    const long P = T * S, R = a46m_rows(T, S, x_per_pair);
-    if (form == 0 && K <= MX4M6_ONE_K) {
-        if (dtype == BIE_F16) return a46m_decode_launch<BIE_F16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-        return a46m_decode_launch<BIE_BF16, true>(x, nullptr, nullptr, idx, qw, sc, ecol, bias, y, P, S, E, N, K, x_per_pair, st);
-    }
-    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* xs = xq + a46m_xs_offset(R, K);
-    uint8_t* rf = xq + a46m_flag_offset(R, K);
-    const int rc = mxfp6_a6_quantize_launch(x, xq, xs, rf, R, K, dtype, st);
-    if (rc) return rc;
-    return mxfp4_moe_a6_gemm_launch(xq, xs, rf, idx, qw, sc, ecol, bias, y, xq + a46m_route_offset(R, K), T, S, E, N, K, x_per_pair, dtype, form, st);
+    return mx_grouped_forward_launch<mx4m6_layer>(x, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
 }  // namespace bie

@@ -26,6 +26,7 @@
 // xq (two 16-byte loads 64 bytes apart), one 16x16x128 MFMA per 16 rows and 128 k; the four partial tiles are summed in LDS in a fixed
 // order.  Prefill form (mx6a8_gemm_kernel): mx_scaled_gemm_tile (FP6 x E4M3) of mx_scaled_tile.cuh.  Both run behind mxa8_quantize_kernel (mxfp4_a8.hip).
 #include "mxfp6_common.cuh"
+#include "mx_scaled_launch.cuh"
 
 #pragma clang fp contract(off)
 
@@ -178,21 +179,6 @@ __global__ __launch_bounds__(256) void mx6a8_gemm_kernel(const uint8_t* __restri
 constexpr int A6_DECODE_ROWS = 64;
 constexpr int A6_PLAN_ROWS = 64;
 
-bool mxfp6_a8_decode_ok(long M) { return M >= 1 && M <= A6_DECODE_ROWS; }
-
-int mxfp6_a8_form(long M, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP6_A8_FORM", -1);
-    if (f == 0 && M <= A6_DECODE_ROWS) return 0;
-    if (f == 1) return 1;
-    return M <= A6_PLAN_ROWS ? 0 : 1;
-}
-
-// Workspace of bie_mxfp6_a8_linear_forward, the layout of the W4A8 one: xq [M, K] (16-byte aligned), xs [M, K/32], row_flag [M]
-static size_t a6_xs_offset(long M, long K) { return (size_t)(M * K); }
-static size_t a6_flag_offset(long M, long K) { return a6_xs_offset(M, K) + (size_t)(M * (K / 32)); }
-size_t mxfp6_a8_workspace_bytes(long M, long K) { return (a6_flag_offset(M, K) + (size_t)M + 15) / 16 * 16; }
-
 int mxfp6_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st) {
     const long nblk = N * (K >> 5);
     const dim3 grid((unsigned)cdivl(nblk, 256));
@@ -211,51 +197,29 @@ int mxfp6_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, 
     return check_launch("mx6_dequant_kernel");
 }
 
-template <int DT, int WM, int WN>
-static void a6_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                             const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const int tn = cdiv(N, 64 * WN);
-    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
-    hipLaunchKernelGGL((mx6a8_gemm_kernel<DT, WM, WN>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
-}
+// Workspace of bie_mxfp6_a8_linear_forward, the layout of the W4A8 one: xq [M, K] (16-byte aligned), xs [M, K/32], row_flag [M]
+struct mx6a8_layer {
+    using act = mx_act_e4m3;  // the W4A8 layer's quantiser and workspace layout
+    static constexpr const char* form_knob = "BIE_MXFP6_A8_FORM";
+    static constexpr int decode_rows = A6_DECODE_ROWS, plan_rows = A6_PLAN_ROWS;
+    static constexpr const char* decode_name = "mx6a8_decode_kernel";
+    static constexpr const char* gemm_name = "mx6a8_gemm_kernel";
+    template <int DT, int G> static constexpr auto decode() { return mx6a8_decode_kernel<DT, G>; }
+    template <int DT, int W> static constexpr auto gemm() { return mx6a8_gemm_kernel<DT, W, W>; }
+};
 
-template <int DT>
-static void a6_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    // 128 x 128 tiles where they give every CU of the card (256) at least two workgroups, else 64 x 64 tiles, as in the W4A8 launcher
-    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) a6_gemm_launch_t<DT, 2, 2>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-    else a6_gemm_launch_t<DT, 1, 1>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-}
-
-template <int DT>
-static void a6_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                                const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const dim3 grid((unsigned)cdiv(N, 16));
-    if (M <= 16) hipLaunchKernelGGL((mx6a8_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else if (M <= 32) hipLaunchKernelGGL((mx6a8_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else hipLaunchKernelGGL((mx6a8_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-}
+bool mxfp6_a8_decode_ok(long M) { return mx_dense_decode_ok<mx6a8_layer>(M); }
+int mxfp6_a8_form(long M, long N, long K, int dtype) { (void)N; (void)K; (void)dtype; return mx_dense_form<mx6a8_layer>(M); }
+size_t mxfp6_a8_workspace_bytes(long M, long K) { return mx_dense_workspace_bytes<mx6a8_layer>(M, K); }
 
 int mxfp6_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
                          const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
-    if (form == 0) {
-        if (dtype == BIE_F16) a6_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        else a6_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        return check_launch("mx6a8_decode_kernel");
-    }
-    if (dtype == BIE_F16) a6_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    else a6_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    return check_launch("mx6a8_gemm_kernel");
+    return mx_dense_gemm_launch<mx6a8_layer>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
 }
 
 int mxfp6_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st) {
-    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* xs = xq + a6_xs_offset(M, K);
-    uint8_t* rf = xq + a6_flag_offset(M, K);
-    const int rc = mxfp4_a8_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
-    if (rc) return rc;
-    return mxfp6_a8_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+    return mx_dense_forward_launch<mx6a8_layer>(x, qw, sc, ecol, bias, y, workspace, M, N, K, dtype, form, st);
 }
 
 }  // namespace bie

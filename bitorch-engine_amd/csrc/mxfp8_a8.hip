@@ -27,6 +27,7 @@
 // 64 bytes apart, so that the 64 lanes of a wave read one whole 128-byte line of each of their 16 weight rows per step.
 // Prefill form (mx8a8_gemm_kernel): mx_scaled_gemm_tile (E4M3 x E4M3) of mx_scaled_tile.cuh on 32x32x64, 4 waves as 2 x 2, double-buffered LDS.
 #include "mxfp4_a8_common.cuh"
+#include "mx_scaled_launch.cuh"
 
 #pragma clang fp contract(off)
 
@@ -208,16 +209,6 @@ __global__ __launch_bounds__(256) void mx8a8_gemm_kernel(const uint8_t* __restri
 constexpr int MX8_DECODE_ROWS = 64;
 constexpr int MX8_PLAN_ROWS = 64;
 
-bool mxfp8_a8_decode_ok(long M) { return M >= 1 && M <= MX8_DECODE_ROWS; }
-
-int mxfp8_a8_form(long M, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP8_A8_FORM", -1);
-    if (f == 0 && M <= MX8_DECODE_ROWS) return 0;
-    if (f == 1) return 1;
-    return M <= MX8_PLAN_ROWS ? 0 : 1;
-}
-
 int mxfp8_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st) {
     const long nunits = N * (K >> 3);
     const dim3 grid((unsigned)cdivl(nunits, 256));
@@ -236,58 +227,35 @@ int mxfp8_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, 
     return check_launch("mx8_dequant_kernel");
 }
 
-template <int DT, int WM, int WN, int BK>
-static void mx8_gemm_launch_t(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                              const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const int tn = cdiv(N, 64 * WN);
-    const dim3 grid((unsigned)(cdiv(M, 64 * WM) * tn));
-    hipLaunchKernelGGL((mx8a8_gemm_kernel<DT, WM, WN, BK>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, tn);
-}
+// The large tile (taken under the shared rule of mx_scaled_launch.cuh: where it gives every CU of the card at least two workgroups) is
+// 128 x 128 at 64 k per stage, the small one 64 x 64 at 128 k per stage.  The large one was measured at M = 4096 against 128 x 64 at
+// 128 k per stage and against 64 x 64 tiles everywhere (the "tile" rows of profiles/mxfp8_a8_bench.jsonl, fp16, us): 243.6 / 252.8 /
+// 251.3 on 4096 x 4096 and 562.4 / 726.5 / 686.3 on 4096 -> 11008, but 673.8 / 629.8 / 716.1 on 11008 -> 4096, where 128 x 64 with the
+// longer stage is 7 % ahead: the tile that wins on two shapes of three ships and the 128 x 64 instance is not kept; a per-call choice
+// was not tried.  A 128 x 128 tile at 128 k per stage in a dynamic allocation of 75776 bytes was not built: nothing in this library
+// launches more than 65536 bytes of LDS.
+// The workspace is bie_mxfp4_a8_linear_forward's: xq [M, K] (16-byte aligned), xs [M, K/32], row_flag [M]
+struct mx8a8_layer {
+    using act = mx_act_e4m3;  // the W4A8 layer's quantiser and workspace layout
+    static constexpr const char* form_knob = "BIE_MXFP8_A8_FORM";
+    static constexpr int decode_rows = MX8_DECODE_ROWS, plan_rows = MX8_PLAN_ROWS;
+    static constexpr const char* decode_name = "mx8a8_decode_kernel";
+    static constexpr const char* gemm_name = "mx8a8_gemm_kernel";
+    template <int DT, int G> static constexpr auto decode() { return mx8a8_decode_kernel<DT, G>; }
+    template <int DT, int W> static constexpr auto gemm() { return mx8a8_gemm_kernel<DT, W, W, W == 2 ? 64 : 128>; }
+};
 
-// Large tiles where they give every CU of the card (256) at least two 128 x 128 workgroups' worth of work, else 64 x 64 tiles, as in the
-// W4A8 launcher.  The large tile is 128 x 128 at 64 k per stage.  It was measured at M = 4096 against 128 x 64 at 128 k per stage and
-// against 64 x 64 tiles everywhere (the "tile" rows of profiles/mxfp8_a8_bench.jsonl, fp16, us): 243.6 / 252.8 / 251.3 on 4096 x 4096
-// and 562.4 / 726.5 / 686.3 on 4096 -> 11008, but 673.8 / 629.8 / 716.1 on 11008 -> 4096, where 128 x 64 with the longer stage is 7 %
-// ahead: the tile that wins on two shapes of three ships and the 128 x 64 instance is not kept; a per-call choice was not tried.  A
-// 128 x 128 tile at 128 k per stage in a dynamic allocation of 75776 bytes was not built: nothing in this library launches more than
-// 65536 bytes of LDS.
-template <int DT>
-static void mx8_gemm_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                               const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    if ((long)cdiv(M, 128) * cdiv(N, 128) >= 512) mx8_gemm_launch_t<DT, 2, 2, 64>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-    else mx8_gemm_launch_t<DT, 1, 1, 128>(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, st);
-}
-
-template <int DT>
-static void mx8_decode_launch_dt(const uint8_t* xq, const uint8_t* xs, const uint8_t* rf, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
-                                 const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const dim3 grid((unsigned)cdiv(N, 16));
-    if (M <= 16) hipLaunchKernelGGL((mx8a8_decode_kernel<DT, 1>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else if (M <= 32) hipLaunchKernelGGL((mx8a8_decode_kernel<DT, 2>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-    else hipLaunchKernelGGL((mx8a8_decode_kernel<DT, 4>), grid, dim3(256), 0, st, xq, xs, rf, qw, sc, ecol, bias, y, M, N, K);
-}
+bool mxfp8_a8_decode_ok(long M) { return mx_dense_decode_ok<mx8a8_layer>(M); }
+int mxfp8_a8_form(long M, long N, long K, int dtype) { (void)N; (void)K; (void)dtype; return mx_dense_form<mx8a8_layer>(M); }
 
 int mxfp8_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol,
                          const void* bias, void* y, long M, long N, long K, int dtype, int form, hipStream_t st) {
-    if (form == 0) {
-        if (dtype == BIE_F16) mx8_decode_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        else mx8_decode_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-        return check_launch("mx8a8_decode_kernel");
-    }
-    if (dtype == BIE_F16) mx8_gemm_launch_dt<BIE_F16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    else mx8_gemm_launch_dt<BIE_BF16>(xq, xs, row_flag, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, st);
-    return check_launch("mx8a8_gemm_kernel");
+    return mx_dense_gemm_launch<mx8a8_layer>(xq, xs, row_flag, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
 }
 
-// The workspace is bie_mxfp4_a8_linear_forward's: xq [M, K] (16-byte aligned), xs [M, K/32], row_flag [M]
 int mxfp8_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st) {
-    uint8_t* xq = reinterpret_cast<uint8_t*>(workspace);
-    uint8_t* xs = xq + (size_t)(M * K);
-    uint8_t* rf = xs + (size_t)(M * (K / 32));
-    const int rc = mxfp4_a8_quantize_launch(x, xq, xs, rf, M, K, dtype, st);
-    if (rc) return rc;
-    return mxfp8_a8_gemm_launch(xq, xs, rf, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
+    return mx_dense_forward_launch<mx8a8_layer>(x, qw, sc, ecol, bias, y, workspace, M, N, K, dtype, form, st);
 }
 
 }  // namespace bie

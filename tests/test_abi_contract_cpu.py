@@ -255,3 +255,38 @@ def test_workspace_bytes_at_and_just_past_the_stated_maxima():
         assert moe(33, SMAX, 3, 32, 0, 0) == 0                      # the decode form stops at P = 1024
     ws = L.bie_mxfp4_moe_workspace_bytes
     assert ws(PMAX, EMAX) > 0 and ws(PMAX + 1, EMAX) == 0 and ws(PMAX, EMAX + 1) == 0 and ws(0, 3) == 0 and ws(1, 1) > 0
+
+
+# ---- the form knobs ------------------------------------------------------------------------------------------------------------------------------
+_KNOB_CHILD = """
+import ctypes, os, sys
+L = ctypes.CDLL(sys.argv[1])
+knob, mine, others, args = sys.argv[2], sys.argv[3], sys.argv[4].split(","), [int(a) for a in sys.argv[5].split(",")]
+def form(name):
+    f = getattr(L, name)
+    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_long] * len(args) + [ctypes.c_int]
+    return f(*args, 0)
+first = [form(mine)] + [form(o) for o in others]
+os.environ[knob] = "0"   # putenv: the C library's getenv sees it
+second = form(mine)
+del os.environ[knob]
+print(*first, second, form(mine))
+"""
+
+
+@pytest.mark.parametrize("knob,mine,others,args", [
+    ("BIE_MXFP4_A6_FORM", "bie_mx4a6_form", ("bie_mxfp4_a4_form", "bie_mxfp4_a8_form", "bie_mxfp6_a6_form", "bie_mxfp6_a8_form", "bie_mx8a8_form"), (1, 8, 64)),
+    ("BIE_MXFP6_MOE_A6_FORM", "bie_mxfp6_moe_a6_form", ("bie_mxfp4_moe_a4_form", "bie_mx4a6_moe_form", "bie_mxfp4_moe_a8_form", "bie_mxfp6_moe_a8_form"),
+     (1, 4, 8, 64))])
+def test_a_form_knob_reaches_its_own_layer_alone_and_is_read_once(knob, mine, others, args):
+    """The layers share one host launch path (csrc/mx_scaled_launch.cuh) and each keeps a knob cache of its own: without BIE_TUNING, a FORM
+    knob set to 1 turns its own layer's plan at M = 1 (P = 1) from the decode form to the prefill form and no other layer's, and the value
+    read at the first call stays when the variable changes or goes away afterwards.  A fresh process: the caches live as long as it does."""
+    import subprocess
+    from bitorch_engine import _hip
+    env = {k: v for k, v in os.environ.items() if k != "BIE_TUNING" and not (k.startswith("BIE_MX") and k.endswith("_FORM"))}
+    env[knob] = "1"
+    p = subprocess.run([sys.executable, "-c", _KNOB_CHILD, _hip.LIB_PATH, knob, mine, ",".join(others), ",".join(map(str, args))],
+                       capture_output=True, text=True, env=env, timeout=60)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.split() == ["1"] + ["0"] * len(others) + ["1", "1"], p.stdout
