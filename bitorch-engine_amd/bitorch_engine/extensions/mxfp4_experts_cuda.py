@@ -11,8 +11,8 @@ synchronises with the host (the routing is read on the device), so every entry c
 import torch
 
 from bitorch_engine import _hip
-from bitorch_engine.extensions import mxfp4_linear_cuda
-from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned
+from bitorch_engine.extensions import _mx_w16, mxfp4_linear_cuda
+from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned  # noqa: F401  (re-exports, as before)
 
 
 def _shape(qweight: torch.Tensor, scales: torch.Tensor):
@@ -52,34 +52,7 @@ def forward(x: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: t
             form: int = -1) -> torch.Tensor:
     """x [T, K] or [T, S, K] (fp16 / bf16), idx int32 [T, S] -> y [T, S, N] in x's dtype.  form -1 = the plan.  e_col (col_exp(scales)) is
     read by the prefill form only: when it is not given and that form is taken, it is computed here."""
-    _hip.need_gpu(x, idx, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 experts: dtype {x.dtype} is not supported (fp16 / bf16)")
-    E, N, K = _shape(qweight, scales)
-    if idx.dtype != torch.int32 or idx.dim() != 2:
-        raise RuntimeError(f"mxfp4 experts: idx must be int32 [T, S] (got {idx.dtype} {tuple(idx.shape)})")
-    T, S = idx.shape
-    if tuple(x.shape) not in ((T, K), (T, S, K)):
-        raise RuntimeError(f"mxfp4 experts: x {tuple(x.shape)} does not match idx {tuple(idx.shape)} and K={K}")
-    y = torch.empty((T, S, N), dtype=x.dtype, device=x.device)
-    if T * S == 0:
-        return y
-    L = _hip.lib()
-    if form < 0:
-        form = int(L.bie_mxfp4_moe_form(T * S, E, N, K, _hip.dt(x)))
-    ws = None
-    if form == 1:
-        if e_col is None:
-            e_col = col_exp(scales)
-        ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(T * S, E)), dtype=torch.uint8, device=x.device)
-    if bias is not None:
-        bias = bias.reshape(E, N).to(dtype=x.dtype).contiguous()
-    x_per_pair = int(x.dim() == 3)
-    x, idx, qweight, scales = _aligned(x), idx.contiguous(), _aligned(qweight), scales.contiguous()  # held until the launches are queued
-    e_col = None if e_col is None else e_col.contiguous()
-    _hip.check(L.bie_mxfp4_moe_forward(_hip.ptr(x), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y),
-                                       _hip.ptr(ws), T, S, E, N, K, x_per_pair, _hip.dt(x), int(form), _hip.stream()), "bie_mxfp4_moe_forward")
-    return y
+    return _LAYER.forward(x, idx, qweight, scales, bias, e_col, form)
 
 
 def blk_exp(scales: torch.Tensor) -> torch.Tensor:
@@ -99,31 +72,7 @@ def grad_input(gy: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scale
     """gy [T, S, N] or [P, N] (fp16 / bf16, any N), idx int32 [T, S] -> gx [P, K], gx[p] = gy[p] . W[idx[p]] (0 for a skipped slot), in
     gy's dtype or, with out_dtype=torch.float32, in fp32 (the caller sums a token's slots before the one rounding).  No image of W is
     built.  e_blk (blk_exp(scales)) is computed here when it is not given."""
-    _hip.need_gpu(gy, idx, qweight, scales, e_blk)
-    if gy.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 experts grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
-    if out_dtype is None:
-        out_dtype = gy.dtype
-    if out_dtype not in (gy.dtype, torch.float32):
-        raise RuntimeError(f"mxfp4 experts grad_input: out_dtype {out_dtype} must be gy's dtype or float32")
-    E, N, K = _shape(qweight, scales)
-    if idx.dtype != torch.int32 or idx.dim() != 2:
-        raise RuntimeError(f"mxfp4 experts: idx must be int32 [T, S] (got {idx.dtype} {tuple(idx.shape)})")
-    T, S = idx.shape
-    P = T * S
-    if tuple(gy.shape) not in ((T, S, N), (P, N)):
-        raise RuntimeError(f"mxfp4 experts grad_input: gy {tuple(gy.shape)} does not match idx {tuple(idx.shape)} and N={N}")
-    gx = torch.empty((P, K), dtype=out_dtype, device=gy.device)
-    if P == 0:
-        return gx
-    L = _hip.lib()
-    if e_blk is None:
-        e_blk = blk_exp(scales)
-    elif e_blk.dtype != torch.uint8 or tuple(e_blk.shape) != (E, K // 32):
-        raise RuntimeError(f"mxfp4 experts grad_input: e_blk must be uint8 [E = {E}, K/32 = {K // 32}]")
-    ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(P, E)), dtype=torch.uint8, device=gy.device)
-    gy, idx, qweight, scales, e_blk = gy.contiguous(), idx.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()
-    _hip.check(L.bie_mxfp4_moe_grad_input(_hip.ptr(gy), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), _hip.ptr(ws),
-                                          T, S, E, N, K, _hip.dt(gy), int(out_dtype == torch.float32), _hip.stream()),
-               "bie_mxfp4_moe_grad_input")
-    return gx
+    return _LAYER.grad_input(gy, idx, qweight, scales, e_blk, out_dtype)
+
+
+_LAYER = _mx_w16.Experts("mxfp4", "mxfp4", _shape, col_exp, blk_exp)

@@ -11,8 +11,8 @@ the host, so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip
-
-_X_DT = (torch.float16, torch.bfloat16)
+from bitorch_engine.extensions import _mx_w16
+from bitorch_engine.extensions._mx_w16 import _X_DT, _aligned  # noqa: F401  (the other MX modules import them from here)
 
 
 def _shape(qweight: torch.Tensor, scales: torch.Tensor):
@@ -22,11 +22,6 @@ def _shape(qweight: torch.Tensor, scales: torch.Tensor):
     if tuple(scales.shape) != (N, K // 32) or K % 32 or K == 0:
         raise RuntimeError(f"mxfp4: scales {tuple(scales.shape)} do not match qweight {tuple(qweight.shape)} (K % 32 == 0 required)")
     return N, K
-
-
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def quantize(weight: torch.Tensor):
@@ -69,26 +64,7 @@ def forward(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: 
             form: int = -1) -> torch.Tensor:
     """x [M, K] (fp16 / bf16) -> y [M, N] in x's dtype.  form -1 = the plan.  e_col (col_exp(scales)) is read by the prefill form only:
     when it is not given and that form is taken, it is computed here."""
-    _hip.need_gpu(x, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 linear: dtype {x.dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    if x.dim() != 2 or x.shape[1] != K:
-        raise RuntimeError(f"mxfp4 linear: x {tuple(x.shape)} does not match K={K}")
-    M = x.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    if M == 0:
-        return y
-    if form < 0:
-        form = int(_hip.lib().bie_mxfp4_form(M, N, K, _hip.dt(x)))
-    if form == 1 and e_col is None:
-        e_col = col_exp(scales)
-    if bias is not None:
-        bias = bias.reshape(-1).to(dtype=x.dtype).contiguous()
-    x, qweight, scales = _aligned(x), _aligned(qweight), scales.contiguous()  # held until the launch is queued
-    _hip.check(_hip.lib().bie_mxfp4_linear_forward(_hip.ptr(x), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y), M, N, K,
-                                                   _hip.dt(x), int(form), _hip.stream()), "bie_mxfp4_linear_forward")
-    return y
+    return _LAYER.forward(x, qweight, scales, bias, e_col, form)
 
 
 def blk_exp(scales: torch.Tensor) -> torch.Tensor:
@@ -106,21 +82,7 @@ def blk_exp(scales: torch.Tensor) -> torch.Tensor:
 def grad_input(gy: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None) -> torch.Tensor:
     """gy [M, N] (fp16 / bf16, any N) -> gx = gy . W [M, K] in gy's dtype, from the packed weight: no image of W is built.  e_blk
     (blk_exp(scales)) is computed here when it is not given."""
-    _hip.need_gpu(gy, qweight, scales, e_blk)
-    if gy.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp4 grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    if gy.dim() != 2 or gy.shape[1] != N:
-        raise RuntimeError(f"mxfp4 grad_input: gy {tuple(gy.shape)} does not match N={N}")
-    M = gy.shape[0]
-    gx = torch.empty((M, K), dtype=gy.dtype, device=gy.device)
-    if M == 0:
-        return gx
-    if e_blk is None:
-        e_blk = blk_exp(scales)
-    elif e_blk.dtype != torch.uint8 or e_blk.numel() != K // 32:
-        raise RuntimeError(f"mxfp4 grad_input: e_blk must be uint8 [K/32 = {K // 32}]")
-    gy, qweight, scales, e_blk = gy.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()  # held until the launch is queued
-    _hip.check(_hip.lib().bie_mxfp4_linear_grad_input(_hip.ptr(gy), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), M, N, K,
-                                                      _hip.dt(gy), _hip.stream()), "bie_mxfp4_linear_grad_input")
-    return gx
+    return _LAYER.grad_input(gy, qweight, scales, e_blk)
+
+
+_LAYER = _mx_w16.Dense("mxfp4", "mxfp4", _shape, col_exp, blk_exp)

@@ -14,7 +14,7 @@ one: the scale bytes are the same).  Nothing here synchronises with the host, so
 import torch
 
 from bitorch_engine import _hip
-from bitorch_engine.extensions import _mx_scaled
+from bitorch_engine.extensions import _mx_scaled, _mx_w16
 from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, blk_exp, col_exp  # noqa: F401
 from bitorch_engine.extensions.mxfp4_a8_linear_cuda import _act_shape, _bias, dequant_act, quantize_act  # noqa: F401
 
@@ -50,6 +50,7 @@ def dequant(qweight: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = to
 
 
 _LAYER = _mx_scaled.Dense("mxfp6_a8", "mxfp6 a8", 32, _shape, col_exp, act_shape=_act_shape)
+_GRAD = _mx_w16.Dense("mxfp6", "mxfp6", _shape, col_exp, blk_exp)  # the input gradient of every MXFP6 weight: it does not see the activations
 
 
 def form(M: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
@@ -73,21 +74,4 @@ def gemm(xq: torch.Tensor, xs: torch.Tensor, row_flag: torch.Tensor, qweight: to
 def grad_input(gy: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, e_blk: torch.Tensor = None) -> torch.Tensor:
     """gy [M, N] (fp16 / bf16, any N) -> gx = gy . W [M, K] in gy's dtype, from the packed weight: no image of W is built.  e_blk
     (blk_exp(scales)) is computed here when it is not given."""
-    _hip.need_gpu(gy, qweight, scales, e_blk)
-    if gy.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    if gy.dim() != 2 or gy.shape[1] != N:
-        raise RuntimeError(f"mxfp6 grad_input: gy {tuple(gy.shape)} does not match N={N}")
-    M = gy.shape[0]
-    gx = torch.empty((M, K), dtype=gy.dtype, device=gy.device)
-    if M == 0:
-        return gx
-    if e_blk is None:
-        e_blk = blk_exp(scales)
-    elif e_blk.dtype != torch.uint8 or e_blk.numel() != K // 32:
-        raise RuntimeError(f"mxfp6 grad_input: e_blk must be uint8 [K/32 = {K // 32}]")
-    gy, qweight, scales, e_blk = gy.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()  # held until the launch is queued
-    _hip.check(_hip.lib().bie_mxfp6_linear_grad_input(_hip.ptr(gy), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), M, N, K,
-                                                      _hip.dt(gy), _hip.stream()), "bie_mxfp6_linear_grad_input")
-    return gx
+    return _GRAD.grad_input(gy, qweight, scales, e_blk)

@@ -15,12 +15,11 @@ and quantize_act / dequant_act are mxfp4_a8_linear_cuda's.  grad_input is the ba
 synchronises with the host (the routing is read on the device), so every entry can be captured in a graph."""
 import torch
 
-from bitorch_engine import _hip
-from bitorch_engine.extensions import _mx_scaled
+from bitorch_engine.extensions import _mx_scaled, _mx_w16
 from bitorch_engine.extensions import mxfp6_a8_linear_cuda
 from bitorch_engine.extensions.mxfp4_a8_linear_cuda import dequant_act, quantize_act  # noqa: F401
 from bitorch_engine.extensions.mxfp4_experts_cuda import blk_exp, col_exp  # noqa: F401
-from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned
+from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned  # noqa: F401  (re-exports, as before)
 
 
 def _shape(qweight: torch.Tensor, scales: torch.Tensor):
@@ -47,6 +46,8 @@ def dequant(qweight: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = to
 
 _LAYER = _mx_scaled.Experts("mxfp6_moe_a8", "mxfp6 a8", 32, _shape, col_exp)
 _idx = _LAYER.idx
+# the input gradient of every MXFP6 expert weight (it does not see the activations); idx is checked under this module's prefix
+_GRAD = _mx_w16.Experts("mxfp6", "mxfp6", _shape, col_exp, blk_exp, idx=_idx)
 _bias = _mx_scaled._experts_bias
 
 
@@ -75,29 +76,4 @@ def grad_input(gy: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scale
     """gy [T, S, N] or [P, N] (fp16 / bf16, any N), idx int32 [T, S] -> gx [P, K], gx[p] = gy[p] . W[idx[p]] (0 for a skipped slot), in
     gy's dtype or, with out_dtype=torch.float32, in fp32 (the caller sums a token's slots before the one rounding).  No image of W is
     built.  e_blk (blk_exp(scales)) is computed here when it is not given."""
-    _hip.need_gpu(gy, idx, qweight, scales, e_blk)
-    if gy.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 experts grad_input: dtype {gy.dtype} is not supported (fp16 / bf16)")
-    if out_dtype is None:
-        out_dtype = gy.dtype
-    if out_dtype not in (gy.dtype, torch.float32):
-        raise RuntimeError(f"mxfp6 experts grad_input: out_dtype {out_dtype} must be gy's dtype or float32")
-    E, N, K = _shape(qweight, scales)
-    T, S = _idx(idx)
-    P = T * S
-    if tuple(gy.shape) not in ((T, S, N), (P, N)):
-        raise RuntimeError(f"mxfp6 experts grad_input: gy {tuple(gy.shape)} does not match idx {tuple(idx.shape)} and N={N}")
-    gx = torch.empty((P, K), dtype=out_dtype, device=gy.device)
-    if P == 0:
-        return gx
-    L = _hip.lib()
-    if e_blk is None:
-        e_blk = blk_exp(scales)
-    elif e_blk.dtype != torch.uint8 or tuple(e_blk.shape) != (E, K // 32):
-        raise RuntimeError(f"mxfp6 experts grad_input: e_blk must be uint8 [E = {E}, K/32 = {K // 32}]")
-    ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(P, E)), dtype=torch.uint8, device=gy.device)
-    gy, idx, qweight, scales, e_blk = gy.contiguous(), idx.contiguous(), _aligned(qweight), scales.contiguous(), e_blk.contiguous()
-    _hip.check(L.bie_mxfp6_moe_grad_input(_hip.ptr(gy), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_blk), _hip.ptr(gx), _hip.ptr(ws),
-                                          T, S, E, N, K, _hip.dt(gy), int(out_dtype == torch.float32), _hip.stream()),
-               "bie_mxfp6_moe_grad_input")
-    return gx
+    return _GRAD.grad_input(gy, idx, qweight, scales, e_blk, out_dtype)

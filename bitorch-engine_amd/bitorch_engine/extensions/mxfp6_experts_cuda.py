@@ -12,9 +12,12 @@ routing is read on the device), so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip
+from bitorch_engine.extensions import _mx_w16
 from bitorch_engine.extensions.mxfp4_experts_cuda import blk_exp, col_exp  # noqa: F401
-from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned
+from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned  # noqa: F401  (re-exports, as before)
 from bitorch_engine.extensions.mxfp6_experts_a8_cuda import _shape, dequant, grad_input, quantize  # noqa: F401
+
+_LAYER = _mx_w16.Experts("mxfp6", "mxfp6", _shape, col_exp, blk_exp)
 
 
 def form(P: int, E: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
@@ -26,31 +29,4 @@ def forward(x: torch.Tensor, idx: torch.Tensor, qweight: torch.Tensor, scales: t
             form: int = -1) -> torch.Tensor:
     """x [T, K] or [T, S, K] (fp16 / bf16), idx int32 [T, S] -> y [T, S, N] in x's dtype.  form -1 = the plan.  e_col (col_exp(scales)) is
     read by the prefill form only: when it is not given and that form is taken, it is computed here."""
-    _hip.need_gpu(x, idx, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 experts: dtype {x.dtype} is not supported (fp16 / bf16)")
-    E, N, K = _shape(qweight, scales)
-    if idx.dtype != torch.int32 or idx.dim() != 2:
-        raise RuntimeError(f"mxfp6 experts: idx must be int32 [T, S] (got {idx.dtype} {tuple(idx.shape)})")
-    T, S = idx.shape
-    if tuple(x.shape) not in ((T, K), (T, S, K)):
-        raise RuntimeError(f"mxfp6 experts: x {tuple(x.shape)} does not match idx {tuple(idx.shape)} and K={K}")
-    y = torch.empty((T, S, N), dtype=x.dtype, device=x.device)
-    if T * S == 0:
-        return y
-    L = _hip.lib()
-    if form < 0:
-        form = int(L.bie_mxfp6_moe_form(T * S, E, N, K, _hip.dt(x)))
-    ws = None
-    if form == 1:
-        if e_col is None:
-            e_col = col_exp(scales)
-        ws = torch.empty(int(L.bie_mxfp4_moe_workspace_bytes(T * S, E)), dtype=torch.uint8, device=x.device)
-    if bias is not None:
-        bias = bias.reshape(E, N).to(dtype=x.dtype).contiguous()
-    x_per_pair = int(x.dim() == 3)
-    x, idx, qweight, scales = _aligned(x), idx.contiguous(), _aligned(qweight), scales.contiguous()  # held until the launches are queued
-    e_col = None if e_col is None else e_col.contiguous()
-    _hip.check(L.bie_mxfp6_moe_forward(_hip.ptr(x), _hip.ptr(idx), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y),
-                                       _hip.ptr(ws), T, S, E, N, K, x_per_pair, _hip.dt(x), int(form), _hip.stream()), "bie_mxfp6_moe_forward")
-    return y
+    return _LAYER.forward(x, idx, qweight, scales, bias, e_col, form)

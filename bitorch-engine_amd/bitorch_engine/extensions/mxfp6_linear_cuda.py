@@ -11,8 +11,11 @@ given).  Nothing here synchronises with the host, so every entry can be captured
 import torch
 
 from bitorch_engine import _hip
+from bitorch_engine.extensions import _mx_w16
 from bitorch_engine.extensions.mxfp4_linear_cuda import _X_DT, _aligned, blk_exp, col_exp  # noqa: F401
 from bitorch_engine.extensions.mxfp6_a8_linear_cuda import _shape, dequant, grad_input, quantize  # noqa: F401
+
+_LAYER = _mx_w16.Dense("mxfp6", "mxfp6", _shape, col_exp, blk_exp)
 
 
 def form(M: int, N: int, K: int, dtype: torch.dtype = torch.float16) -> int:
@@ -24,23 +27,4 @@ def forward(x: torch.Tensor, qweight: torch.Tensor, scales: torch.Tensor, bias: 
             form: int = -1) -> torch.Tensor:
     """x [M, K] (fp16 / bf16) -> y [M, N] in x's dtype.  form -1 = the plan.  e_col (col_exp(scales)) is read by the prefill form only:
     when it is not given and that form is taken, it is computed here."""
-    _hip.need_gpu(x, qweight, scales, bias, e_col)
-    if x.dtype not in _X_DT:
-        raise RuntimeError(f"mxfp6 linear: dtype {x.dtype} is not supported (fp16 / bf16)")
-    N, K = _shape(qweight, scales)
-    if x.dim() != 2 or x.shape[1] != K:
-        raise RuntimeError(f"mxfp6 linear: x {tuple(x.shape)} does not match K={K}")
-    M = x.shape[0]
-    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-    if M == 0:
-        return y
-    if form < 0:
-        form = int(_hip.lib().bie_mxfp6_form(M, N, K, _hip.dt(x)))
-    if form == 1 and e_col is None:
-        e_col = col_exp(scales)
-    if bias is not None:
-        bias = bias.reshape(-1).to(dtype=x.dtype).contiguous()
-    x, qweight, scales = _aligned(x), _aligned(qweight), scales.contiguous()  # held until the launch is queued
-    _hip.check(_hip.lib().bie_mxfp6_linear_forward(_hip.ptr(x), _hip.ptr(qweight), _hip.ptr(scales), _hip.ptr(e_col), _hip.ptr(bias), _hip.ptr(y), M, N, K,
-                                                   _hip.dt(x), int(form), _hip.stream()), "bie_mxfp6_linear_forward")
-    return y
+    return _LAYER.forward(x, qweight, scales, bias, e_col, form)

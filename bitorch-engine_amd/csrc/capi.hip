@@ -129,6 +129,7 @@ int mxfp4_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, 
 int mxfp4_col_exp_launch(const uint8_t* sc, uint8_t* ecol, long N, long K, hipStream_t st);
 int mxfp4_form(long M, long N, long K, int dtype);
 bool mxfp4_decode_ok(long M);
+int mxfp4_decode_rows();
 // mxfp4_a4.hip
 int mxfp4_a4_form(long M, long N, long K, int dtype);
 bool mxfp4_a4_decode_ok(long M);
@@ -1096,19 +1097,43 @@ int bie_mxfp4_col_exp(const uint8_t* scales, uint8_t* e_col, long N, long K, voi
 
 int bie_mxfp4_form(long M, long N, long K, int dtype) { return mxfp4_form(M, N, K, dtype); }
 
+// One entry check for the weight-only layers and their input gradients (MXFP4 and MXFP6 weights against fp16 / bf16 activations; their
+// host side is csrc/mx_w16_launch.cuh).  A row names the format's functions; the expert and gradient helpers are further down, after
+// the checks they share with the block-scaled layers.
+struct mx_w16_entry {
+    decltype(mxfp4_form)* form;
+    decltype(mxfp4_decode_ok)* decode_ok;
+    decltype(mxfp4_decode_rows)* decode_rows;
+    decltype(mxfp4_forward_launch)* forward;
+    decltype(mxfp4_moe_form)* moe_form;
+    decltype(mxfp4_moe_decode_ok)* moe_decode_ok;
+    decltype(mxfp4_moe_forward_launch)* moe_forward;
+    decltype(mxfp4_grad_input_launch)* grad_input;
+    decltype(mxfp4_moe_grad_input_launch)* moe_grad_input;
+};
+static const mx_w16_entry MX_W4A16 = {mxfp4_form,          mxfp4_decode_ok,          mxfp4_decode_rows,       mxfp4_forward_launch,       mxfp4_moe_form,
+                                      mxfp4_moe_decode_ok, mxfp4_moe_forward_launch, mxfp4_grad_input_launch, mxfp4_moe_grad_input_launch};
+static const mx_w16_entry MX_W6A16 = {mxfp6_form,          mxfp6_decode_ok,          mxfp6_decode_rows,       mxfp6_forward_launch,       mxfp6_moe_form,
+                                      mxfp6_moe_decode_ok, mxfp6_moe_forward_launch, mxfp6_grad_input_launch, mxfp6_moe_grad_input_launch};
+
+static int mx_w16_forward(const mx_w16_entry& L, const char* fn, const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
+                          const void* bias, void* y, long M, long N, long K, int dtype, int form, void* stream) {
+    int rc = check_mx(fn, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld (M >= 1 required)", fn, M);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, form);
+    if (form < 0) form = L.form(M, N, K, dtype);
+    BIE_REQUIRE(form == 1 || L.decode_ok(M), BIE_ERR_UNSUPPORTED, "%s: the decode form takes M <= %d (M=%ld)", fn, L.decode_rows(), M);
+    BIE_REQUIRE(x && qweight && scales && y && (form == 0 || e_col), BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer (the prefill form needs e_col)", fn);
+    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(y, 2) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
+                "%s: x and qweight must be 16-byte aligned, y and bias 2-byte aligned", fn);
+    return L.forward(x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+}
+
 int bie_mxfp4_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
                              long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mx("bie_mxfp4_linear_forward", N, K);
-    if (rc) return rc;
-    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: M=%ld (M >= 1 required)", M);
-    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "bie_mxfp4_linear_forward: dtype %d (0=f16, 1=bf16)", dtype);
-    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: form %d (-1 = plan, 0 = decode, 1 = prefill)", form);
-    if (form < 0) form = mxfp4_form(M, N, K, dtype);
-    BIE_REQUIRE(form == 1 || mxfp4_decode_ok(M), BIE_ERR_UNSUPPORTED, "bie_mxfp4_linear_forward: the decode form takes M <= 16 (M=%ld)", M);
-    BIE_REQUIRE(x && qweight && scales && y && (form == 0 || e_col), BIE_ERR_INVALID_ARG, "bie_mxfp4_linear_forward: NULL tensor pointer (the prefill form needs e_col)");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(y, 2) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp4_linear_forward: x and qweight must be 16-byte aligned, y and bias 2-byte aligned");
-    return mxfp4_forward_launch(x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_w16_forward(MX_W4A16, "bie_mxfp4_linear_forward", x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP4 W4A4.  Everything is checked here, before any device call.
@@ -1335,15 +1360,7 @@ int bie_mxfp6_form(long M, long N, long K, int dtype) { return mxfp6_form(M, N, 
 
 int bie_mxfp6_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
                              long N, long K, int dtype, int form, void* stream) {
-    int rc = check_mxa4("bie_mxfp6_linear_forward", M, N, K, dtype);
-    if (rc) return rc;
-    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "bie_mxfp6_linear_forward: form %d (-1 = plan, 0 = decode, 1 = prefill)", form);
-    if (form < 0) form = mxfp6_form(M, N, K, dtype);
-    BIE_REQUIRE(form == 1 || mxfp6_decode_ok(M), BIE_ERR_UNSUPPORTED, "bie_mxfp6_linear_forward: the decode form takes M <= %d (M=%ld)", mxfp6_decode_rows(), M);
-    BIE_REQUIRE(x && qweight && scales && y && (form == 0 || e_col), BIE_ERR_INVALID_ARG, "bie_mxfp6_linear_forward: NULL tensor pointer (the prefill form needs e_col)");
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(y, 2) && !misaligned(bias, 2), BIE_ERR_INVALID_ARG,
-                "bie_mxfp6_linear_forward: x and qweight must be 16-byte aligned, y and bias 2-byte aligned");
-    return mxfp6_forward_launch(x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, as_stream(stream));
+    return mx_w16_forward(MX_W6A16, "bie_mxfp6_linear_forward", x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP4 mixture of experts.  Everything is checked here, before any device call.
@@ -1353,14 +1370,21 @@ int bie_mxfp4_moe_form(long P, long E, long N, long K, int dtype) { return mxfp4
 
 size_t bie_mxfp4_moe_workspace_bytes(long P, long E) { return mx_moe_pairs_ok(P, E) ? mxfp4_moe_workspace_bytes(P, E) : 0; }
 
-int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
-                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp4_moe_forward";
+// the shape and routing limits that the weight-only expert forward and its input gradient share
+static int check_mx_w16_routed(const char* fn, long T, long S, long E, long N, long K) {
     int rc = check_mx(fn, N, K);
     if (rc) return rc;
     BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
     BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
     BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
+    return BIE_OK;
+}
+
+static int mx_w16_moe_forward(const mx_w16_entry& L, const char* fn, const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                              const uint8_t* e_col, const void* bias, void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair,
+                              int dtype, int form, void* stream) {
+    int rc = check_mx_w16_routed(fn, T, S, E, N, K);
+    if (rc) return rc;
     const long P = T * S;
     BIE_REQUIRE(N <= (1L << 31) - 128, BIE_ERR_UNSUPPORTED, "%s: N=%ld beyond 2^31 - 128 (the column tiles are counted in int)", fn, N);
     BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((N + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
@@ -1368,42 +1392,27 @@ int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qwei
     BIE_REQUIRE(x_per_pair == 0 || x_per_pair == 1, BIE_ERR_INVALID_ARG, "%s: x_per_pair %d (0 = x is [T, K], 1 = x is [P, K])", fn, x_per_pair);
     BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
     BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, form);
-    if (form < 0) form = mxfp4_moe_form(P, E, N, K, dtype);
-    BIE_REQUIRE(form == 1 || mxfp4_moe_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
+    if (form < 0) form = L.moe_form(P, E, N, K, dtype);
+    BIE_REQUIRE(form == 1 || L.moe_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
     BIE_REQUIRE(x && idx && qweight && scales && y && (form == 0 || (e_col && workspace)), BIE_ERR_INVALID_ARG,
                 "%s: NULL tensor pointer (the prefill form needs e_col and the workspace)", fn);
     BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 2) && !misaligned(bias, 2) &&
                     (form == 0 || !misaligned(workspace, 16)),
                 BIE_ERR_INVALID_ARG, "%s: x, qweight and workspace must be 16-byte aligned, idx 4-byte, y and bias 2-byte aligned", fn);
-    return mxfp4_moe_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return L.moe_forward(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
 }
 
-// ---- MXFP6 weight-only (W6A16) mixture of experts: bie_mxfp4_moe_forward's checks line for line, the workspace bie_mxfp4_moe_workspace_bytes.
+int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                          void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    return mx_w16_moe_forward(MX_W4A16, "bie_mxfp4_moe_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
+}
+
+// ---- MXFP6 weight-only (W6A16) mixture of experts: the MXFP4 layer's entry check, the workspace bie_mxfp4_moe_workspace_bytes.
 int bie_mxfp6_moe_form(long P, long E, long N, long K, int dtype) { return mxfp6_moe_form(P, E, N, K, dtype); }
 
 int bie_mxfp6_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                           void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
-    const char* fn = "bie_mxfp6_moe_forward";
-    int rc = check_mx(fn, N, K);
-    if (rc) return rc;
-    BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
-    BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
-    BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
-    const long P = T * S;
-    BIE_REQUIRE(N <= (1L << 31) - 128, BIE_ERR_UNSUPPORTED, "%s: N=%ld beyond 2^31 - 128 (the column tiles are counted in int)", fn, N);
-    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((N + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
-                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
-    BIE_REQUIRE(x_per_pair == 0 || x_per_pair == 1, BIE_ERR_INVALID_ARG, "%s: x_per_pair %d (0 = x is [T, K], 1 = x is [P, K])", fn, x_per_pair);
-    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
-    BIE_REQUIRE(form >= -1 && form <= 1, BIE_ERR_INVALID_ARG, "%s: form %d (-1 = plan, 0 = decode, 1 = prefill)", fn, form);
-    if (form < 0) form = mxfp6_moe_form(P, E, N, K, dtype);
-    BIE_REQUIRE(form == 1 || mxfp6_moe_decode_ok(P), BIE_ERR_UNSUPPORTED, "%s: the decode form takes P <= 1024 (P=%ld)", fn, P);
-    BIE_REQUIRE(x && idx && qweight && scales && y && (form == 0 || (e_col && workspace)), BIE_ERR_INVALID_ARG,
-                "%s: NULL tensor pointer (the prefill form needs e_col and the workspace)", fn);
-    BIE_REQUIRE(!misaligned(x, 16) && !misaligned(qweight, 16) && !misaligned(idx, 4) && !misaligned(y, 2) && !misaligned(bias, 2) &&
-                    (form == 0 || !misaligned(workspace, 16)),
-                BIE_ERR_INVALID_ARG, "%s: x, qweight and workspace must be 16-byte aligned, idx 4-byte, y and bias 2-byte aligned", fn);
-    return mxfp6_moe_forward_launch(x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, as_stream(stream));
+    return mx_w16_moe_forward(MX_W6A16, "bie_mxfp6_moe_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 // ---- The block-scaled MX expert layers (W4A4, W4A8, W6A8, W6A6, W4A6; their host side is csrc/mx_scaled_launch.cuh): one entry check.
@@ -1597,9 +1606,8 @@ int bie_mxfp4_blk_exp(const uint8_t* scales, uint8_t* e_blk, long rows, long K, 
     return mxfp4_blk_exp_launch(scales, e_blk, rows, K, groups, as_stream(stream));
 }
 
-int bie_mxfp4_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
-                                int dtype, void* stream) {
-    const char* fn = "bie_mxfp4_linear_grad_input";
+static int mx_w16_grad_input(const mx_w16_entry& L, const char* fn, const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk,
+                             void* gx, long M, long N, long K, int dtype, void* stream) {
     int rc = check_mx(fn, N, K);
     if (rc) return rc;
     BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld (M >= 1 required)", fn, M);
@@ -1608,60 +1616,44 @@ int bie_mxfp4_linear_grad_input(const void* gy, const uint8_t* qweight, const ui
     BIE_REQUIRE(gy && qweight && scales && e_blk && gx, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
     BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(qweight, 16) && !misaligned(gx, 16), BIE_ERR_INVALID_ARG,
                 "%s: qweight and gx must be 16-byte aligned, gy 2-byte aligned", fn);
-    return mxfp4_grad_input_launch(gy, qweight, scales, e_blk, gx, M, N, K, dtype, as_stream(stream));
+    return L.grad_input(gy, qweight, scales, e_blk, gx, M, N, K, dtype, as_stream(stream));
+}
+
+static int mx_w16_moe_grad_input(const mx_w16_entry& L, const char* fn, const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales,
+                                 const uint8_t* e_blk, void* gx, void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32,
+                                 void* stream) {
+    int rc = check_mx_w16_routed(fn, T, S, E, N, K);
+    if (rc) return rc;
+    const long P = T * S;
+    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
+                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(out_fp32 == 0 || out_fp32 == 1, BIE_ERR_INVALID_ARG, "%s: out_fp32 %d (0 = gx in the dtype, 1 = gx in fp32)", fn, out_fp32);
+    BIE_REQUIRE(gy && idx && qweight && scales && e_blk && gx && workspace, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
+    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(idx, 4) && !misaligned(qweight, 16) && !misaligned(gx, 16) && !misaligned(workspace, 16),
+                BIE_ERR_INVALID_ARG, "%s: qweight, gx and workspace must be 16-byte aligned, idx 4-byte, gy 2-byte aligned", fn);
+    return L.moe_grad_input(gy, idx, qweight, scales, e_blk, gx, workspace, P, E, N, K, dtype, out_fp32, as_stream(stream));
+}
+
+int bie_mxfp4_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
+                                int dtype, void* stream) {
+    return mx_w16_grad_input(MX_W4A16, "bie_mxfp4_linear_grad_input", gy, qweight, scales, e_blk, gx, M, N, K, dtype, stream);
 }
 
 int bie_mxfp4_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                              void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
-    const char* fn = "bie_mxfp4_moe_grad_input";
-    int rc = check_mx(fn, N, K);
-    if (rc) return rc;
-    BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
-    BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
-    BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
-    const long P = T * S;
-    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
-                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
-    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
-    BIE_REQUIRE(out_fp32 == 0 || out_fp32 == 1, BIE_ERR_INVALID_ARG, "%s: out_fp32 %d (0 = gx in the dtype, 1 = gx in fp32)", fn, out_fp32);
-    BIE_REQUIRE(gy && idx && qweight && scales && e_blk && gx && workspace, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
-    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(idx, 4) && !misaligned(qweight, 16) && !misaligned(gx, 16) && !misaligned(workspace, 16),
-                BIE_ERR_INVALID_ARG, "%s: qweight, gx and workspace must be 16-byte aligned, idx 4-byte, gy 2-byte aligned", fn);
-    return mxfp4_moe_grad_input_launch(gy, idx, qweight, scales, e_blk, gx, workspace, P, E, N, K, dtype, out_fp32, as_stream(stream));
+    return mx_w16_moe_grad_input(MX_W4A16, "bie_mxfp4_moe_grad_input", gy, idx, qweight, scales, e_blk, gx, workspace, T, S, E, N, K, dtype, out_fp32, stream);
 }
 
-// ---- MXFP6 input gradient: the MXFP4 entries' checks on the MXFP6 weight format (bie_mxfp4_blk_exp serves both).
+// ---- MXFP6 input gradient: the same checks on the MXFP6 weight format (bie_mxfp4_blk_exp serves both).
 int bie_mxfp6_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
                                 int dtype, void* stream) {
-    const char* fn = "bie_mxfp6_linear_grad_input";
-    int rc = check_mx(fn, N, K);
-    if (rc) return rc;
-    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld (M >= 1 required)", fn, M);
-    BIE_REQUIRE(((M + 127) / 128) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: M=%ld, K=%ld beyond the tile count's range", fn, M, K);
-    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
-    BIE_REQUIRE(gy && qweight && scales && e_blk && gx, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
-    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(qweight, 16) && !misaligned(gx, 16), BIE_ERR_INVALID_ARG,
-                "%s: qweight and gx must be 16-byte aligned, gy 2-byte aligned", fn);
-    return mxfp6_grad_input_launch(gy, qweight, scales, e_blk, gx, M, N, K, dtype, as_stream(stream));
+    return mx_w16_grad_input(MX_W6A16, "bie_mxfp6_linear_grad_input", gy, qweight, scales, e_blk, gx, M, N, K, dtype, stream);
 }
 
 int bie_mxfp6_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                              void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
-    const char* fn = "bie_mxfp6_moe_grad_input";
-    int rc = check_mx(fn, N, K);
-    if (rc) return rc;
-    BIE_REQUIRE(E >= 1 && E <= 1024, BIE_ERR_INVALID_ARG, "%s: E=%ld (1 <= E <= 1024 required)", fn, E);
-    BIE_REQUIRE(S >= 1 && S <= 32, BIE_ERR_INVALID_ARG, "%s: S=%ld (1 <= S <= 32 required)", fn, S);
-    BIE_REQUIRE(T >= 1 && T <= (1L << 22) && T * S <= (1L << 22), BIE_ERR_INVALID_ARG, "%s: T=%ld, S=%ld (1 <= T * S <= 2^22 required)", fn, T, S);
-    const long P = T * S;
-    BIE_REQUIRE(E * N < (1L << 31) && P * N < (1L << 40) && (P / 128 + E + 1) * ((K + 127) / 128) < (1L << 31), BIE_ERR_UNSUPPORTED,
-                "%s: E * N = %ld or P * N = %ld beyond the layer's range", fn, E * N, P * N);
-    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
-    BIE_REQUIRE(out_fp32 == 0 || out_fp32 == 1, BIE_ERR_INVALID_ARG, "%s: out_fp32 %d (0 = gx in the dtype, 1 = gx in fp32)", fn, out_fp32);
-    BIE_REQUIRE(gy && idx && qweight && scales && e_blk && gx && workspace, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
-    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(idx, 4) && !misaligned(qweight, 16) && !misaligned(gx, 16) && !misaligned(workspace, 16),
-                BIE_ERR_INVALID_ARG, "%s: qweight, gx and workspace must be 16-byte aligned, idx 4-byte, gy 2-byte aligned", fn);
-    return mxfp6_moe_grad_input_launch(gy, idx, qweight, scales, e_blk, gx, workspace, P, E, N, K, dtype, out_fp32, as_stream(stream));
+    return mx_w16_moe_grad_input(MX_W6A16, "bie_mxfp6_moe_grad_input", gy, idx, qweight, scales, e_blk, gx, workspace, T, S, E, N, K, dtype, out_fp32, stream);
 }
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.

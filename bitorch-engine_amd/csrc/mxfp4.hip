@@ -17,6 +17,7 @@
 // (bie_mxfp4_col_exp, computed once at load time): fragments hold e2m1 * 2^(s - e_col[n]) <= 6 and the fp32 epilogue multiplies by
 // 2^(e_col[n] - 127).  A column with a scale-255 block has e_col = 255, which makes the whole column NaN in the epilogue.
 #include "mxfp4_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
@@ -175,16 +176,6 @@ __global__ __launch_bounds__(256) void mx_gemm_kernel(const uint16_t* __restrict
 constexpr int MX_DECODE_ROWS = 16;
 constexpr int MX_PLAN_ROWS = 16;
 
-int mxfp4_form(long M, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP4_FORM", -1);
-    if (f == 0 && M <= MX_DECODE_ROWS) return 0;
-    if (f == 1) return 1;
-    return M <= MX_PLAN_ROWS ? 0 : 1;
-}
-
-bool mxfp4_decode_ok(long M) { return M >= 1 && M <= MX_DECODE_ROWS; }
-
 int mxfp4_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st) {
     const long nblk = N * (K / 32);
     const dim3 grid((unsigned)cdivl(nblk, 256));
@@ -214,28 +205,28 @@ static void mx_decode_launch_r(const uint16_t* x, const uint8_t* qw, const uint8
     hipLaunchKernelGGL((mx_decode_kernel<DT, R, C>), dim3((unsigned)cdiv(N, C)), dim3(256), 0, st, x, qw, sc, bias, y, M, N, K);
 }
 
-template <int DT>
-static void mx_decode_launch_dt(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    if (M <= 1) mx_decode_launch_r<DT, 1>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 2) mx_decode_launch_r<DT, 2>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 4) mx_decode_launch_r<DT, 4>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 8) mx_decode_launch_r<DT, 8>(x, qw, sc, bias, y, M, N, K, st);
-    else mx_decode_launch_r<DT, 16>(x, qw, sc, bias, y, M, N, K, st);
-}
+// the layer, for the host path of mx_w16_launch.cuh
+struct mx4_w16_layer {
+    static constexpr const char* form_knob = "BIE_MXFP4_FORM";
+    static constexpr int decode_rows = MX_DECODE_ROWS, plan_rows = MX_PLAN_ROWS;
+    static constexpr const char *decode_name = "mx_decode_kernel", *gemm_name = "mx_gemm_kernel";
+    template <int DT>
+    static void decode(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+        if (M <= 1) mx_decode_launch_r<DT, 1>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 2) mx_decode_launch_r<DT, 2>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 4) mx_decode_launch_r<DT, 4>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 8) mx_decode_launch_r<DT, 8>(x, qw, sc, bias, y, M, N, K, st);
+        else mx_decode_launch_r<DT, 16>(x, qw, sc, bias, y, M, N, K, st);
+    }
+    template <int DT> static constexpr auto gemm() { return mx_gemm_kernel<DT>; }
+};
 
+int mxfp4_form(long M, long, long, int) { return mx_w16_form<mx4_w16_layer>(M); }
+bool mxfp4_decode_ok(long M) { return mx_w16_decode_ok<mx4_w16_layer>(M); }
+int mxfp4_decode_rows() { return MX_DECODE_ROWS; }
 int mxfp4_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
                          int dtype, int form, hipStream_t st) {
-    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
-    if (form == 0) {
-        if (dtype == BIE_F16) mx_decode_launch_dt<BIE_F16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
-        else mx_decode_launch_dt<BIE_BF16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
-        return check_launch("mx_decode_kernel");
-    }
-    const int tn = (int)cdivl(N, MX_BN);
-    const dim3 grid((unsigned)(cdivl(M, MX_BM) * tn));
-    if (dtype == BIE_F16) hipLaunchKernelGGL(mx_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
-    else hipLaunchKernelGGL(mx_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
-    return check_launch("mx_gemm_kernel");
+    return mx_w16_forward_launch<mx4_w16_layer>(x, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
 }
 
 }  // namespace bie

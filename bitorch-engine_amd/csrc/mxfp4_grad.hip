@@ -32,14 +32,11 @@
 // they are: a row tile belongs to one expert, gathers its gy rows by the pair list and scatters gx[pair]; the tiles of the skipped bin
 // store zeros and run no loop.  Nothing synchronises with the host.
 #include "mxfp4_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-// mxfp4_moe.hip: the routing launch and its workspace layout, shared as they are
-long mxfp4_moe_max_tiles(long P, long E);
-int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
 
 static_assert(MXM_BM == MX_DG_BM, "a row tile of the routing is a row tile of mx_dgrad_tile");
 
@@ -92,38 +89,21 @@ int mxfp4_blk_exp_launch(const uint8_t* sc, uint8_t* eblk, long rows, long K, lo
     return check_launch("mx_blk_exp_kernel");
 }
 
-// gy rows in whole 16-byte pieces where every row starts on one
-static int dgrad_vec(const void* gy, long N) { return (N % 8 == 0 && reinterpret_cast<uintptr_t>(gy) % 16 == 0) ? 1 : 0; }
+// the unit, for the host path of mx_w16_launch.cuh (the routing launch and its workspace layout are mxfp4_moe.hip's, shared as they are)
+struct mx4_dgrad_unit {
+    static constexpr int BM = MX_DG_BM, BK = MX_DG_BK;
+    static constexpr const char *dense_name = "mx_dgrad_kernel", *grouped_name = "mxm_dgrad_kernel";
+    template <int DT> static constexpr auto dense() { return mx_dgrad_kernel<DT>; }
+    template <int DT, int ODT> static constexpr auto grouped() { return mxm_dgrad_kernel<DT, ODT>; }
+};
 
 int mxfp4_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, long M, long N, long K, int dtype,
                             hipStream_t st) {
-    const uint16_t* g = reinterpret_cast<const uint16_t*>(gy);
-    const int tk = (int)cdivl(K, MX_DG_BK), vec = dgrad_vec(gy, N);
-    const dim3 grid((unsigned)(cdivl(M, MX_DG_BM) * tk));
-    if (dtype == BIE_F16) hipLaunchKernelGGL(mx_dgrad_kernel<BIE_F16>, grid, dim3(256), 0, st, g, qw, sc, eblk, gx, (int)M, (int)N, (int)K, tk, vec);
-    else hipLaunchKernelGGL(mx_dgrad_kernel<BIE_BF16>, grid, dim3(256), 0, st, g, qw, sc, eblk, gx, (int)M, (int)N, (int)K, tk, vec);
-    return check_launch("mx_dgrad_kernel");
+    return mx_w16_grad_input_launch<mx4_dgrad_unit>(gy, qw, sc, eblk, gx, M, N, K, dtype, st);
 }
-
 int mxfp4_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
                                 long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st) {
-    const uint16_t* g = reinterpret_cast<const uint16_t*>(gy);
-    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
-    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E), vec = dgrad_vec(gy, N);
-    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(max_tiles * cdivl(K, MX_DG_BK)));
-#define BIE_MXM_DGRAD(DT, ODT) \
-    hipLaunchKernelGGL((mxm_dgrad_kernel<DT, ODT>), grid, dim3(256), 0, st, g, ws, qw, sc, eblk, gx, (int)E, (int)N, (int)K, vec, max_tiles)
-    if (dtype == BIE_F16) {
-        if (out_fp32) BIE_MXM_DGRAD(BIE_F16, BIE_F32);
-        else BIE_MXM_DGRAD(BIE_F16, BIE_F16);
-    } else {
-        if (out_fp32) BIE_MXM_DGRAD(BIE_BF16, BIE_F32);
-        else BIE_MXM_DGRAD(BIE_BF16, BIE_BF16);
-    }
-#undef BIE_MXM_DGRAD
-    return check_launch("mxm_dgrad_kernel");
+    return mx_w16_moe_grad_input_launch<mx4_dgrad_unit>(gy, idx, qw, sc, eblk, gx, workspace, P, E, N, K, dtype, out_fp32, st);
 }
 
 }  // namespace bie

@@ -22,6 +22,7 @@
 //   rows through the pair list, each row in whole 16-byte pieces; rows past the segment load as zero and are not stored; the epilogue
 //   scatters row r to y[pair r].  The tiles of the skipped bin run no K loop and store zeros.
 #include "mxfp4_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
@@ -30,6 +31,11 @@ namespace bie {
 // ---- routed decode form -------------------------------------------------------------------------------------------------------------------
 // Workgroup: pair blockIdx.y, columns C * blockIdx.x .. + C - 1 of its expert (clamped reads past N, never stored).  Thread t takes the
 // 16-value units u = t, t + 256, ... of K: per column 8 code bytes and the scale byte of block u / 2.
+// It keeps a body of its own beside mx_decode_kernel's (mxfp4.hip), whose arithmetic it repeats for one row.  One body for both (the
+// dense kernel's, called here with one row and the expert's row offset) kept registers, LDS and zero scratch but was slower at 64 pairs
+// on 4096 x 4096, E = 32: shared / own body, us by graph replay, medians of three rounds, in two runs of the comparison: fp16
+// 114.26 / 112.48 and 115.32 / 114.63, bf16 113.19 / 111.77 and 114.20 / 113.16, against 0.4 - 0.9 us between two arms of the own body.
+// tests/test_mxfp4_moe_gpu.py holds the two bodies to the same bits.
 template <int DT, int C>
 __global__ __launch_bounds__(256) void mxm_decode_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw,
                                                          const uint8_t* __restrict__ sc, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
@@ -201,16 +207,6 @@ __global__ __launch_bounds__(256) void mxm_gemm_kernel(const uint16_t* __restric
 constexpr int MXM_DECODE_PAIRS = 1024;
 constexpr int MXM_PLAN_PAIRS = 64, MXM_PLAN_PAIRS_SPARSE = 256;
 
-int mxfp4_moe_form(long P, long E, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP4_MOE_FORM", -1);
-    if (f == 0 && P <= MXM_DECODE_PAIRS) return 0;
-    if (f == 1) return 1;
-    return (P <= MXM_PLAN_PAIRS || (P <= MXM_PLAN_PAIRS_SPARSE && P <= 2 * E)) ? 0 : 1;
-}
-
-bool mxfp4_moe_decode_ok(long P) { return P >= 1 && P <= MXM_DECODE_PAIRS; }
-
 size_t mxfp4_moe_workspace_bytes(long P, long E) {
     const size_t words = (size_t)MXM_HEAD + 3 * (size_t)mxm_max_tiles(P, E) + (size_t)P;
     return (words * 4 + 15) / 16 * 16;
@@ -224,29 +220,25 @@ int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, 
     return check_launch("mxm_route_kernel");
 }
 
+// the layer, for the host path of mx_w16_launch.cuh
+struct mx4m_w16_layer {
+    static constexpr const char* form_knob = "BIE_MXFP4_MOE_FORM";
+    static constexpr int decode_pairs = MXM_DECODE_PAIRS, plan_pairs = MXM_PLAN_PAIRS, plan_pairs_sparse = MXM_PLAN_PAIRS_SPARSE;
+    static constexpr const char *decode_name = "mxm_decode_kernel", *gemm_name = "mxm_gemm_kernel";
+    template <int DT>
+    static void decode(const uint16_t* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int P, int S, int E, int N,
+                       int K, int x_per_pair, hipStream_t st) {
+        constexpr int C = 4;  // mx_decode_kernel's one-row instance
+        hipLaunchKernelGGL((mxm_decode_kernel<DT, C>), dim3((unsigned)cdiv(N, C), (unsigned)P), dim3(256), 0, st, x, idx, qw, sc, bias, y, S, E, N, K, x_per_pair);
+    }
+    template <int DT> static constexpr auto gemm() { return mxm_gemm_kernel<DT>; }
+};
+
+int mxfp4_moe_form(long P, long E, long, long, int) { return mx_w16_moe_form<mx4m_w16_layer>(P, E); }
+bool mxfp4_moe_decode_ok(long P) { return mx_w16_moe_decode_ok<mx4m_w16_layer>(P); }
 int mxfp4_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                              void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
-    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
-    const long P = T * S;
-    if (form == 0) {
-        constexpr int C = 4;
-        const dim3 grid((unsigned)cdivl(N, C), (unsigned)P);
-        if (dtype == BIE_F16)
-            hipLaunchKernelGGL((mxm_decode_kernel<BIE_F16, C>), grid, dim3(256), 0, st, xs, idx, qw, sc, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair);
-        else
-            hipLaunchKernelGGL((mxm_decode_kernel<BIE_BF16, C>), grid, dim3(256), 0, st, xs, idx, qw, sc, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair);
-        return check_launch("mxm_decode_kernel");
-    }
-    int32_t* ws = reinterpret_cast<int32_t*>(workspace);
-    const int max_tiles = (int)mxm_max_tiles(P, E);
-    int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, MX_BN)));
-    if (dtype == BIE_F16)
-        hipLaunchKernelGGL(mxm_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
-    else
-        hipLaunchKernelGGL(mxm_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
-    return check_launch("mxm_gemm_kernel");
+    return mx_w16_moe_forward_launch<mx4m_w16_layer>(x, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
 }  // namespace bie

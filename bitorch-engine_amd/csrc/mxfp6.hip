@@ -22,6 +22,7 @@
 // the LDS read, one pk32 convert per 32 weights.  Each column is rebiased by its largest scale code e_col[n] (bie_mxfp4_col_exp):
 // fragments hold e2m3 * 2^(s - e_col[n]) <= 7.5 and the fp32 epilogue multiplies by 2^(e_col[n] - 127); e_col = 255 makes the column NaN.
 #include "mxfp6_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
@@ -139,54 +140,37 @@ __global__ __launch_bounds__(256) void mx6_gemm_kernel(const uint16_t* __restric
 constexpr int MX6_DECODE_ROWS = 32;
 constexpr int MX6_PLAN_ROWS = 32;
 
-int mxfp6_form(long M, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP6_FORM", -1);
-    if (f == 0 && M <= MX6_DECODE_ROWS) return 0;
-    if (f == 1) return 1;
-    return M <= MX6_PLAN_ROWS ? 0 : 1;
-}
-
-bool mxfp6_decode_ok(long M) { return M >= 1 && M <= MX6_DECODE_ROWS; }
-int mxfp6_decode_rows() { return MX6_DECODE_ROWS; }
-
-template <int DT, int R, int G>
-static void mx6_decode_launch_g(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    constexpr int CT = (G == 32 || R >= 32) ? 2 : 4, C = CT * (256 / G);
-    hipLaunchKernelGGL((mx6_decode_kernel<DT, R, CT, G>), dim3((unsigned)cdiv(N, C)), dim3(256), 0, st, x, qw, sc, bias, y, M, N, K);
-}
-
 template <int DT, int R>
 static void mx6_decode_launch_r(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    const int g = mx6_decode_group(K >> 5);
-    if (g == 128) mx6_decode_launch_g<DT, R, 128>(x, qw, sc, bias, y, M, N, K, st);
-    else if (g == 64) mx6_decode_launch_g<DT, R, 64>(x, qw, sc, bias, y, M, N, K, st);
-    else mx6_decode_launch_g<DT, R, 32>(x, qw, sc, bias, y, M, N, K, st);
+    mx6_decode_group(K >> 5, [&](auto g) {
+        constexpr int G = decltype(g)::value, CT = (G == 32 || R >= 32) ? 2 : 4, C = CT * (256 / G);
+        hipLaunchKernelGGL((mx6_decode_kernel<DT, R, CT, G>), dim3((unsigned)cdiv(N, C)), dim3(256), 0, st, x, qw, sc, bias, y, M, N, K);
+    });
 }
 
-template <int DT>
-static void mx6_decode_launch_dt(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
-    if (M <= 1) mx6_decode_launch_r<DT, 1>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 2) mx6_decode_launch_r<DT, 2>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 4) mx6_decode_launch_r<DT, 4>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 8) mx6_decode_launch_r<DT, 8>(x, qw, sc, bias, y, M, N, K, st);
-    else if (M <= 16) mx6_decode_launch_r<DT, 16>(x, qw, sc, bias, y, M, N, K, st);
-    else mx6_decode_launch_r<DT, 32>(x, qw, sc, bias, y, M, N, K, st);
-}
+// the layer, for the host path of mx_w16_launch.cuh
+struct mx6_w16_layer {
+    static constexpr const char* form_knob = "BIE_MXFP6_FORM";
+    static constexpr int decode_rows = MX6_DECODE_ROWS, plan_rows = MX6_PLAN_ROWS;
+    static constexpr const char *decode_name = "mx6_decode_kernel", *gemm_name = "mx6_gemm_kernel";
+    template <int DT>
+    static void decode(const uint16_t* x, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int M, int N, int K, hipStream_t st) {
+        if (M <= 1) mx6_decode_launch_r<DT, 1>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 2) mx6_decode_launch_r<DT, 2>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 4) mx6_decode_launch_r<DT, 4>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 8) mx6_decode_launch_r<DT, 8>(x, qw, sc, bias, y, M, N, K, st);
+        else if (M <= 16) mx6_decode_launch_r<DT, 16>(x, qw, sc, bias, y, M, N, K, st);
+        else mx6_decode_launch_r<DT, 32>(x, qw, sc, bias, y, M, N, K, st);
+    }
+    template <int DT> static constexpr auto gemm() { return mx6_gemm_kernel<DT>; }
+};
 
+int mxfp6_form(long M, long, long, int) { return mx_w16_form<mx6_w16_layer>(M); }
+bool mxfp6_decode_ok(long M) { return mx_w16_decode_ok<mx6_w16_layer>(M); }
+int mxfp6_decode_rows() { return MX6_DECODE_ROWS; }
 int mxfp6_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
                          int dtype, int form, hipStream_t st) {
-    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
-    if (form == 0) {
-        if (dtype == BIE_F16) mx6_decode_launch_dt<BIE_F16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
-        else mx6_decode_launch_dt<BIE_BF16>(xs, qw, sc, bias, y, (int)M, (int)N, (int)K, st);
-        return check_launch("mx6_decode_kernel");
-    }
-    const int tn = (int)cdivl(N, MX_BN);
-    const dim3 grid((unsigned)(cdivl(M, MX_BM) * tn));
-    if (dtype == BIE_F16) hipLaunchKernelGGL(mx6_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
-    else hipLaunchKernelGGL(mx6_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, qw, sc, ecol, bias, y, (int)M, (int)N, (int)K, tn);
-    return check_launch("mx6_gemm_kernel");
+    return mx_w16_forward_launch<mx6_w16_layer>(x, qw, sc, ecol, bias, y, M, N, K, dtype, form, st);
 }
 
 }  // namespace bie

@@ -10,6 +10,7 @@
 // which the instructions read a lane's six operand registers (tools/probe/probe_mx_fp6.hip part (a2), profiles/mxfp6_a8_probe.txt), so
 // a lane's fragment is a plain 24-byte copy.  Code bits: bit 5 sign, bits 4:3 exponent (bias 1), bits 2:0 mantissa; no Inf / NaN code.
 #pragma once
+#include <type_traits>
 #include "mxfp4_a8_common.cuh"
 
 namespace bie {
@@ -476,12 +477,13 @@ __device__ __forceinline__ float mx6_half_sum_f32(float v) {
     return dpp_add<0x142, 0xa>(v);
 }
 
-// (host; shared by the decode forms of mxfp6.hip and mxfp6_moe.hip)
-// threads per column group: the largest of 128, 64, 32 whose padded last pass wastes at most an eighth of the passes' slots, else 32
-static int mx6_decode_group(int KB) {
-    for (int g = 128; g > 32; g >>= 1)
-        if ((long)cdiv(KB, g) * g * 8 <= (long)KB * 9) return g;
-    return 32;
+// (host) The decode forms' dispatch over the group width, for mxfp6.hip and mxfp6_moe.hip: f(std::integral_constant<int, G>) with G the
+// threads per column group, the largest of 128, 64, 32 whose padded last pass wastes at most an eighth of the passes' slots, else 32.
+template <class F>
+static void mx6_decode_group(int KB, F&& f) {
+    if ((long)cdiv(KB, 128) * 128 * 8 <= (long)KB * 9) f(std::integral_constant<int, 128>{});
+    else if ((long)cdiv(KB, 64) * 64 * 8 <= (long)KB * 9) f(std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 32>{});
 }
 
 }  // namespace bie

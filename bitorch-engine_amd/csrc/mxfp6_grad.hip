@@ -40,14 +40,11 @@
 // kernel uses the routing workspace and launch of mxfp4_moe.hip as they are: a row tile belongs to one expert, gathers its gy rows by
 // the pair list and scatters gx[pair]; the tiles of the skipped bin store zeros and run no loop.  Nothing synchronises with the host.
 #include "mxfp6_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
-
-// mxfp4_moe.hip: the routing launch and its workspace layout, shared as they are
-long mxfp4_moe_max_tiles(long P, long E);
-int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
 
 static_assert(MXM_BM == MX6_DG_BM, "a row tile of the routing is a row tile of mx6_dgrad_tile");
 
@@ -76,38 +73,21 @@ __global__ __launch_bounds__(256) void mx6m_dgrad_kernel(const uint16_t* __restr
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------------------
-// gy rows in whole 16-byte pieces where every row starts on one
-static int dgrad6_vec(const void* gy, long N) { return (N % 8 == 0 && reinterpret_cast<uintptr_t>(gy) % 16 == 0) ? 1 : 0; }
+// the unit, for the host path of mx_w16_launch.cuh (the routing launch and its workspace layout are mxfp4_moe.hip's, shared as they are)
+struct mx6_dgrad_unit {
+    static constexpr int BM = MX6_DG_BM, BK = MX6_DG_BK;
+    static constexpr const char *dense_name = "mx6_dgrad_kernel", *grouped_name = "mx6m_dgrad_kernel";
+    template <int DT> static constexpr auto dense() { return mx6_dgrad_kernel<DT>; }
+    template <int DT, int ODT> static constexpr auto grouped() { return mx6m_dgrad_kernel<DT, ODT>; }
+};
 
 int mxfp6_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, long M, long N, long K, int dtype,
                             hipStream_t st) {
-    const uint16_t* g = reinterpret_cast<const uint16_t*>(gy);
-    const int tk = (int)cdivl(K, MX6_DG_BK), vec = dgrad6_vec(gy, N);
-    const dim3 grid((unsigned)(cdivl(M, MX6_DG_BM) * tk));
-    if (dtype == BIE_F16) hipLaunchKernelGGL(mx6_dgrad_kernel<BIE_F16>, grid, dim3(256), 0, st, g, qw, sc, eblk, gx, (int)M, (int)N, (int)K, tk, vec);
-    else hipLaunchKernelGGL(mx6_dgrad_kernel<BIE_BF16>, grid, dim3(256), 0, st, g, qw, sc, eblk, gx, (int)M, (int)N, (int)K, tk, vec);
-    return check_launch("mx6_dgrad_kernel");
+    return mx_w16_grad_input_launch<mx6_dgrad_unit>(gy, qw, sc, eblk, gx, M, N, K, dtype, st);
 }
-
 int mxfp6_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
                                 long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st) {
-    const uint16_t* g = reinterpret_cast<const uint16_t*>(gy);
-    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
-    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E), vec = dgrad6_vec(gy, N);
-    const int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(max_tiles * cdivl(K, MX6_DG_BK)));
-#define BIE_MX6M_DGRAD(DT, ODT) \
-    hipLaunchKernelGGL((mx6m_dgrad_kernel<DT, ODT>), grid, dim3(256), 0, st, g, ws, qw, sc, eblk, gx, (int)E, (int)N, (int)K, vec, max_tiles)
-    if (dtype == BIE_F16) {
-        if (out_fp32) BIE_MX6M_DGRAD(BIE_F16, BIE_F32);
-        else BIE_MX6M_DGRAD(BIE_F16, BIE_F16);
-    } else {
-        if (out_fp32) BIE_MX6M_DGRAD(BIE_BF16, BIE_F32);
-        else BIE_MX6M_DGRAD(BIE_BF16, BIE_BF16);
-    }
-#undef BIE_MX6M_DGRAD
-    return check_launch("mx6m_dgrad_kernel");
+    return mx_w16_moe_grad_input_launch<mx6_dgrad_unit>(gy, idx, qw, sc, eblk, gx, workspace, P, E, N, K, dtype, out_fp32, st);
 }
 
 }  // namespace bie

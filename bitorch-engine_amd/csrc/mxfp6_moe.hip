@@ -25,18 +25,20 @@
 // not stored; the epilogue scatters row r to y[pair r].  A row's K order is the dense tile's, so a pair's row has the bits of the dense
 // prefill form.  The tiles of the skipped bin run no K loop and store zeros.
 #include "mxfp6_common.cuh"
+#include "mx_w16_launch.cuh"
 
 #pragma clang fp contract(off)
 
 namespace bie {
 
-// mxfp4_moe.hip
-long mxfp4_moe_max_tiles(long P, long E);
-int mxfp4_moe_route_launch(const int32_t* idx, void* workspace, long P, long E, hipStream_t st);
-
 // ---- routed decode form -------------------------------------------------------------------------------------------------------------------
 // Workgroup: pair blockIdx.y, columns C * blockIdx.x .. + C - 1 of its expert, C = CT * 256 / G (clamped reads past N, never stored).
 // Group g = t / G holds columns g CT .. + CT - 1 of those; its thread j = t % G takes the blocks j, j + G, ... of K.
+// It keeps a body of its own beside mx6_decode_kernel's (mxfp6.hip).  One body for both (the dense kernel's, called here with one row
+// and the expert's row offset) kept registers, LDS and zero scratch but was slower at 64 pairs on 2880 -> 5760, E = 32: shared / own
+// body, us by graph replay, medians of three rounds, in two runs of the comparison: fp16 186.54 / 185.75 and 186.35 / 185.64, bf16
+// 187.68 / 187.12 and 187.29 / 186.49, against 0.4 - 0.6 us between two arms of the own body.  tests/test_mxfp6_moe_gpu.py holds the
+// two bodies to the same bits.
 template <int DT, int CT, int G>
 __global__ __launch_bounds__(256) void mx6m_decode_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ idx, const uint8_t* __restrict__ qw,
                                                           const uint8_t* __restrict__ sc, const void* __restrict__ bias, void* __restrict__ y, int S, int E,
@@ -122,6 +124,12 @@ __global__ __launch_bounds__(256) void mx6m_decode_kernel(const uint16_t* __rest
 static_assert(MXM_BM == MX_BM, "a row tile of the routing is a row tile of mx6_gemm_tile");
 static_assert(2 * MX6_STAGE + MXM_BM * 4 <= 65536, "static LDS");
 
+// mx6_gemm_tile stays a body of its own beside mx_gemm_tile (mxfp4_common.cuh), with which it shares the x staging, the loop frame and
+// the epilogue as text.  One frame over a weight-side type (slots, load / store, B fragments, the A fragment's 16 bytes) kept
+// registers, LDS and zero scratch, and the MXFP4 GEMMs came out 2 - 5 % faster, but this kernel was slower at 512 pairs on 2880 -> 5760,
+// E = 32: shared frame / own body, us by graph replay, medians of three rounds, in two runs of the comparison: fp16 285.65 / 283.36 and
+// 284.70 / 283.22, bf16 285.56 / 283.72 and 285.11 / 282.98, against 0.4 - 1.2 us between two arms of the own body.  A frame that only
+// some of its four kernels may use is more code than the two bodies, so all four keep theirs.
 template <int DT>
 __global__ __launch_bounds__(256) void mx6m_gemm_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ ws, const uint8_t* __restrict__ qw,
                                                         const uint8_t* __restrict__ sc, const uint8_t* __restrict__ ecol, const void* __restrict__ bias,
@@ -155,52 +163,28 @@ __global__ __launch_bounds__(256) void mx6m_gemm_kernel(const uint16_t* __restri
 constexpr int MX6M_DECODE_PAIRS = 1024;
 constexpr int MX6M_PLAN_PAIRS = 64, MX6M_PLAN_PAIRS_SPARSE = 256;
 
-int mxfp6_moe_form(long P, long E, long N, long K, int dtype) {
-    (void)N; (void)K; (void)dtype;
-    const int f = BIE_KNOB("BIE_MXFP6_MOE_FORM", -1);
-    if (f == 0 && P <= MX6M_DECODE_PAIRS) return 0;
-    if (f == 1) return 1;
-    return (P <= MX6M_PLAN_PAIRS || (P <= MX6M_PLAN_PAIRS_SPARSE && P <= 2 * E)) ? 0 : 1;
-}
+// the layer, for the host path of mx_w16_launch.cuh
+struct mx6m_w16_layer {
+    static constexpr const char* form_knob = "BIE_MXFP6_MOE_FORM";
+    static constexpr int decode_pairs = MX6M_DECODE_PAIRS, plan_pairs = MX6M_PLAN_PAIRS, plan_pairs_sparse = MX6M_PLAN_PAIRS_SPARSE;
+    static constexpr const char *decode_name = "mx6m_decode_kernel", *gemm_name = "mx6m_gemm_kernel";
+    template <int DT>
+    static void decode(const uint16_t* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int P, int S, int E, int N,
+                       int K, int x_per_pair, hipStream_t st) {
+        mx6_decode_group(K >> 5, [&](auto g) {
+            constexpr int G = decltype(g)::value, CT = G == 32 ? 2 : 4, C = CT * (256 / G);  // mx6_decode_kernel's one-row instance
+            hipLaunchKernelGGL((mx6m_decode_kernel<DT, CT, G>), dim3((unsigned)cdiv(N, C), (unsigned)P), dim3(256), 0, st, x, idx, qw, sc, bias, y, S, E, N,
+                               K, x_per_pair);
+        });
+    }
+    template <int DT> static constexpr auto gemm() { return mx6m_gemm_kernel<DT>; }
+};
 
-bool mxfp6_moe_decode_ok(long P) { return P >= 1 && P <= MX6M_DECODE_PAIRS; }
-
-template <int DT, int G>
-static void mx6m_decode_launch_g(const uint16_t* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int P, int S, int E,
-                                 int N, int K, int x_per_pair, hipStream_t st) {
-    constexpr int CT = G == 32 ? 2 : 4, C = CT * (256 / G);  // mxfp6.hip's one-row instance
-    hipLaunchKernelGGL((mx6m_decode_kernel<DT, CT, G>), dim3((unsigned)cdiv(N, C), (unsigned)P), dim3(256), 0, st, x, idx, qw, sc, bias, y, S, E, N, K,
-                       x_per_pair);
-}
-
-template <int DT>
-static void mx6m_decode_launch_dt(const uint16_t* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const void* bias, void* y, int P, int S, int E,
-                                  int N, int K, int x_per_pair, hipStream_t st) {
-    const int g = mx6_decode_group(K >> 5);
-    if (g == 128) mx6m_decode_launch_g<DT, 128>(x, idx, qw, sc, bias, y, P, S, E, N, K, x_per_pair, st);
-    else if (g == 64) mx6m_decode_launch_g<DT, 64>(x, idx, qw, sc, bias, y, P, S, E, N, K, x_per_pair, st);
-    else mx6m_decode_launch_g<DT, 32>(x, idx, qw, sc, bias, y, P, S, E, N, K, x_per_pair, st);
-}
-
+int mxfp6_moe_form(long P, long E, long, long, int) { return mx_w16_moe_form<mx6m_w16_layer>(P, E); }
+bool mxfp6_moe_decode_ok(long P) { return mx_w16_moe_decode_ok<mx6m_w16_layer>(P); }
 int mxfp6_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
                              void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st) {
-    const uint16_t* xs = reinterpret_cast<const uint16_t*>(x);
-    const long P = T * S;
-    if (form == 0) {
-        if (dtype == BIE_F16) mx6m_decode_launch_dt<BIE_F16>(xs, idx, qw, sc, bias, y, (int)P, (int)S, (int)E, (int)N, (int)K, x_per_pair, st);
-        else mx6m_decode_launch_dt<BIE_BF16>(xs, idx, qw, sc, bias, y, (int)P, (int)S, (int)E, (int)N, (int)K, x_per_pair, st);
-        return check_launch("mx6m_decode_kernel");
-    }
-    const int32_t* ws = reinterpret_cast<const int32_t*>(workspace);
-    const int max_tiles = (int)mxfp4_moe_max_tiles(P, E);
-    int rc = mxfp4_moe_route_launch(idx, workspace, P, E, st);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(max_tiles * cdivl(N, MX_BN)));
-    if (dtype == BIE_F16)
-        hipLaunchKernelGGL(mx6m_gemm_kernel<BIE_F16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
-    else
-        hipLaunchKernelGGL(mx6m_gemm_kernel<BIE_BF16>, grid, dim3(256), 0, st, xs, ws, qw, sc, ecol, bias, y, (int)S, (int)E, (int)N, (int)K, x_per_pair, max_tiles);
-    return check_launch("mx6m_gemm_kernel");
+    return mx_w16_moe_forward_launch<mx6m_w16_layer>(x, idx, qw, sc, ecol, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, st);
 }
 
 }  // namespace bie

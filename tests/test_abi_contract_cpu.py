@@ -277,9 +277,14 @@ print(*first, second, form(mine))
 @pytest.mark.parametrize("knob,mine,others,args", [
     ("BIE_MXFP4_A6_FORM", "bie_mx4a6_form", ("bie_mxfp4_a4_form", "bie_mxfp4_a8_form", "bie_mxfp6_a6_form", "bie_mxfp6_a8_form", "bie_mx8a8_form"), (1, 8, 64)),
     ("BIE_MXFP6_MOE_A6_FORM", "bie_mxfp6_moe_a6_form", ("bie_mxfp4_moe_a4_form", "bie_mx4a6_moe_form", "bie_mxfp4_moe_a8_form", "bie_mxfp6_moe_a8_form"),
-     (1, 4, 8, 64))])
+     (1, 4, 8, 64)),
+    ("BIE_MXFP4_FORM", "bie_mxfp4_form", ("bie_mxfp6_form",), (1, 8, 64)),
+    ("BIE_MXFP6_FORM", "bie_mxfp6_form", ("bie_mxfp4_form",), (1, 8, 64)),
+    ("BIE_MXFP4_MOE_FORM", "bie_mxfp4_moe_form", ("bie_mxfp6_moe_form",), (1, 4, 8, 64)),
+    ("BIE_MXFP6_MOE_FORM", "bie_mxfp6_moe_form", ("bie_mxfp4_moe_form",), (1, 4, 8, 64))])
 def test_a_form_knob_reaches_its_own_layer_alone_and_is_read_once(knob, mine, others, args):
-    """The layers share one host launch path (csrc/mx_scaled_launch.cuh) and each keeps a knob cache of its own: without BIE_TUNING, a FORM
+    """The layers share one host launch path (csrc/mx_scaled_launch.cuh, and csrc/mx_w16_launch.cuh for the weight-only layers, whose four
+    form functions are each checked against their twin of the other format) and each keeps a knob cache of its own: without BIE_TUNING, a FORM
     knob set to 1 turns its own layer's plan at M = 1 (P = 1) from the decode form to the prefill form and no other layer's, and the value
     read at the first call stays when the variable changes or goes away afterwards.  A fresh process: the caches live as long as it does."""
     import subprocess

@@ -88,7 +88,8 @@ def test_dequant_is_exact():
 
 SHAPES = [(M, K, N) for M in (1, 2, 3, 8, 16, 17, 64) for K, N in ((32, 1), (96, 7), (4096, 33))] + \
          [(M, K, N) for M in (1, 8, 16, 17, 64) for K, N in ((4096, 4096), (11008, 33), (96, 4096))] + \
-         [(4096, 4096, 33), (4096, 96, 4096), (4096, 11008, 7), (4096, 4096, 4096)]
+         [(4096, 4096, 33), (4096, 96, 4096), (4096, 11008, 7), (4096, 4096, 4096)] + \
+         [(M, 96, 7) for M in (4, 5, 9)]  # a full 4-row decode instance, the first rows of the 8-row and the 16-row instance
 
 
 @pytest.mark.parametrize("dt", DTS)

@@ -195,6 +195,31 @@ def test_exact_data_is_bit_identical_across_forms_and_to_the_linear_layer(T, xpp
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("xpp", [0, 1])
+# (32, 1): two units, 254 idle threads; (96, 7): N is no multiple of C = 4, the clamped reads; (4128, 33): 258 units, two threads take a
+# second trip; (2880, 33): gpt-oss's K
+@pytest.mark.parametrize("K,N", [(32, 1), (96, 7), (4128, 33), (2880, 33)])
+def test_routed_decode_form_equals_the_dense_decode_form_bit_for_bit_on_inexact_data(K, N, xpp, dt):
+    """Gaussian x, random weights and a bias: the sums round, and a live pair's row still has the bits of MXFP4LinearCuda's decode form
+    at M = 1 on its expert, because the unit-to-thread map and the order of the sums are the same.  A skipped pair's row is +0."""
+    E, S, T = 3, 2, 5
+    q, s, _ = rand_mx(E, N, K, 71)
+    g = torch.Generator().manual_seed(72 + xpp)
+    x = torch.randn((T, S, K) if xpp else (T, K), generator=g).to(dt).to(DEV)
+    bias = torch.randn((E, N), generator=g).to(dt).to(DEV)
+    idx = torch.randint(0, E, (T, S), generator=g, dtype=torch.int32)
+    idx[1, 1], idx[3, 0] = -1, E
+    y = ext().forward(x, idx.to(DEV), q, s, bias, form=0).reshape(T * S, N)
+    xr = (x if xpp else x[:, None, :].expand(T, S, K)).reshape(T * S, K)
+    for p, e in enumerate(idx.reshape(-1).tolist()):
+        if not 0 <= e < E:
+            assert (y[p].view(torch.int16) == 0).all(), (p, e)  # +0: no sign bit
+            continue
+        want = lin().forward(xr[p:p + 1].contiguous(), q[e], s[e], bias[e], form=0)[0]
+        assert torch.equal(y[p].view(torch.int16), want.view(torch.int16)), (p, e)
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("xpp", [0, 1])
 def test_grouped_prefill_form_equals_the_dense_prefill_form_bit_for_bit_on_inexact_data(xpp, dt):
     """Random normal x, random weights and a bias: the sums round, and the grouped prefill form still gives the bits of the linear
     layer's prefill form called once per expert on that expert's rows, because both run the one tile body (mx_gemm_tile) and a row's

@@ -53,7 +53,8 @@ def weights(K, N):
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("K,N", [(32, 1), (96, 7), (2880, 33), (4096, 129), (96, 4096)])
-@pytest.mark.parametrize("M", sorted({1, 2, 3, 8, B, B + 1, 64, 129, 300}))
+# M = 17 and M = B = 32: the first and the last row of the 32-row decode instance
+@pytest.mark.parametrize("M", sorted({1, 2, 3, 8, 17, B, B + 1, 64, 129, 300}))
 def test_forward_both_forms_against_float64(M, K, N, dt):
     qd, sd, W = weights(K, N)
     g = torch.Generator().manual_seed(M * 7 + K * 3 + N)

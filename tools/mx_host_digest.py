@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""One line per host-side answer of the block-scaled MX layers' C entry points (six dense: W4A4, W4A6, W4A8, W6A6, W6A8, W8A8; five
-grouped: W4A4, W4A6, W4A8, W6A6, W6A8 experts).  No GPU is needed: every call is a host function or fails its entry check before any
+"""One line per host-side answer of the MX layers' C entry points: the block-scaled layers (six dense: W4A4, W4A6, W4A8, W6A6, W6A8, W8A8;
+five grouped: W4A4, W4A6, W4A8, W6A6, W6A8 experts), then the weight-only layers (MXFP4 and MXFP6 x fp16 / bf16: linear, experts and
+their input gradients).  No GPU is needed: every call is a host function or fails its entry check before any
 device call.  Two builds of the library have the same plans, workspace sizes, return codes and error texts exactly when their listings
 are equal line for line.
 
@@ -9,7 +10,9 @@ are equal line for line.
 Lines: every *_form (dense at M = 0 .. 130, grouped at P x E below) with the layer's FORM knob unset, 0 and 1 under BIE_TUNING; every
 *_workspace_bytes over a grid that crosses each stated limit; and the return code and bie_last_error text of every forward and gemm
 entry under one broken argument at a time: K, M / T, N, S, E, x_per_pair, dtype, form, the decode form past its row or pair bound, each
-NULL pointer and each misaligned pointer."""
+NULL pointer and each misaligned pointer.  The weight-only lines follow those (so the block-scaled listing stays as recorded): the four
+*_form functions under their knobs unset, 0 and 1, bie_mxfp4_moe_workspace_bytes, and the refusals of the four forward entries, the four
+grad_input entries and bie_mxfp4_blk_exp."""
 import os
 import sys
 
@@ -117,12 +120,51 @@ def entries(L):
         print(f"{stem}_forward decode K=65536 NULL workspace rc={rc} {L.bie_last_error().decode()}")
 
 
+def weight_only(L):
+    for fmt in ("mxfp4", "mxfp6"):
+        name = f"BIE_{fmt.upper()}_FORM"
+        for v in (None, "0", "1"):
+            knob(name, v)
+            print(f"bie_{fmt}_form {name}={v}", *[getattr(L, f"bie_{fmt}_form")(M, 8, 64, M & 1) for M in range(131)])
+        knob(name, None)
+    for fmt in ("mxfp4", "mxfp6"):
+        name = f"BIE_{fmt.upper()}_MOE_FORM"
+        for v in (None, "0", "1"):
+            knob(name, v)
+            for E in EXPERTS:
+                print(f"bie_{fmt}_moe_form {name}={v} E={E}", *[getattr(L, f"bie_{fmt}_moe_form")(P, E, 8, 64, P & 1) for P in PAIRS])
+        knob(name, None)
+    for E in (0, 1, 32, 1024, 1025):
+        print(f"bie_mxfp4_moe_workspace_bytes E={E}", *[L.bie_mxfp4_moe_workspace_bytes(P, E) for P in (0, 1, 127, 128, 129, 4096, 1 << 22, (1 << 22) + 1)])
+    shape = (("K", (0, 48, (1 << 20) + 32, -32)), ("N", (0, 1 << 31)))
+    dense = shape + (("M", (0, -1, 1 << 31)), ("dtype", (-1, 2, 3)), (("M", "K"), ((1 << 21, 1 << 20),)), (("M", "N"), ((1 << 21, 1 << 20),)))
+    routed = shape + (("T", (0, -1, (1 << 22) + 1)), ("S", (0, 33)), ("E", (0, 1025)), ("dtype", (-1, 2)), (("T", "S"), ((1 << 22, 2),)),
+                      (("E", "N"), ((1024, 1 << 21),)), (("T", "S", "N"), ((1 << 22, 1, 1 << 18),)))
+    for fmt in ("mxfp4", "mxfp6"):
+        # x, qweight, scales, e_col, bias, y; form 1: e_col is needed
+        refusals(L, f"bie_{fmt}_linear_forward", [FAKE] * 4 + [None, FAKE], {0: 16, 1: 16, 4: 2, 5: 2}, dict(M=1, N=8, K=64, dtype=0, form=1),
+                 dense + (("form", (-2, 2)), (("M", "form"), ((33, 0), (65, 0), (4096, 0)))))
+        # x, idx, qweight, scales, e_col, bias, y, workspace; form 1: e_col and the workspace are needed
+        refusals(L, f"bie_{fmt}_moe_forward", [FAKE] * 5 + [None, FAKE, FAKE], {0: 16, 1: 4, 2: 16, 5: 2, 6: 2, 7: 16},
+                 dict(T=1, S=4, E=3, N=8, K=64, x_per_pair=0, dtype=0, form=1),
+                 routed + (("N", ((1 << 31) - 127,)), ("x_per_pair", (-1, 2)), ("form", (-2, 2)), (("T", "S", "form"), ((1025, 1, 0), (257, 4, 0)))))
+        # gy, qweight, scales, e_blk, gx
+        refusals(L, f"bie_{fmt}_linear_grad_input", [FAKE] * 5, {0: 2, 1: 16, 4: 16}, dict(M=1, N=8, K=64, dtype=0), dense)
+        # gy, idx, qweight, scales, e_blk, gx, workspace
+        refusals(L, f"bie_{fmt}_moe_grad_input", [FAKE] * 7, {0: 2, 1: 4, 2: 16, 5: 16, 6: 16}, dict(T=1, S=4, E=3, N=8, K=64, dtype=0, out_fp32=0),
+                 routed + (("out_fp32", (-1, 2)),))
+    # scales, e_blk
+    refusals(L, "bie_mxfp4_blk_exp", [FAKE] * 2, {}, dict(rows=8, K=64, groups=1),
+             (("rows", (0, 1 << 31)), ("K", (0, 48, (1 << 20) + 32)), ("groups", (0, 1025)), (("groups", "rows"), ((1024, 1 << 21),))))
+
+
 def main():
     from bitorch_engine import _hip
     L = _hip.lib()
     forms(L)
     workspaces(L)
     entries(L)
+    weight_only(L)
 
 
 if __name__ == "__main__":

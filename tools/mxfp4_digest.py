@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""One SHA-256 of y's bytes per case for the MX layers, every form forced: the weight-only MXFP4 layers and every layer on the shared
+"""One SHA-256 of y's bytes per case for the MX layers, every form forced: the weight-only MXFP4 and MXFP6 layers and every layer on the shared
 block-scaled tile (mx_scaled_gemm_tile: W4A4, W4A6, W4A8, W6A6, W6A8, W8A8 linear; W4A4, W4A6, W4A8, W6A6, W6A8 experts), whose decode
 forms are on mx_scaled_decode_rows / mx_scaled_decode_pair or on bodies of their own.  Two builds of the library compute the same bits exactly when their listings are
 equal line for line.
@@ -13,7 +13,10 @@ expert layers with x per token and per pair at E = 3, S = 4, 96 -> 33 (T in {1, 
 {16, 300}), and the two grouped A6 layers once more at E = 3, T = 300 under each value of their tile width knob (BIE_MXFP4_MOE_A6_WN,
 BIE_MXFP6_MOE_A6_WN); the five expert A-layers' gemm entry at form 0 on the outputs of their quantize_act (the routed kernel that reads
 xq from memory, which forward never runs at these K) at E = 3, T in {1, 17}, and forward and gemm at T = 17 under each strip width
-of the three layers that have the knob (BIE_MXFP4_MOE_A4_STRIP, BIE_MXFP4_MOE_A8_STRIP, BIE_MXFP6_MOE_A8_STRIP = 1, 2, 4)."""
+of the three layers that have the knob (BIE_MXFP4_MOE_A4_STRIP, BIE_MXFP4_MOE_A8_STRIP, BIE_MXFP6_MOE_A8_STRIP = 1, 2, 4).  Last, on
+streams of their own, gx of the four input-gradient entries (MXFP4 and MXFP6): dense at M in {1, 129, 300} on 96 -> 33 (N % 8 != 0: the
+guarded 16-bit loads of gy) and 2880 -> 2880 (whole 16-byte pieces), grouped at E = 3, S = 4, T in {1, 17, 300} on both shapes with gx
+in the dtype and in fp32."""
 import hashlib
 import importlib
 import os
@@ -39,11 +42,15 @@ EXPERTS = ((3, 4, 96, 33, (1, 17, 300)), (32, 4, 2880, 2880, (16, 300)))
 # (extension, name in the listing, bits per weight code, largest M of the decode form)
 LINEAR = (("mxfp4_linear_cuda", "linear", 4, 16), ("mxfp4_a4_linear_cuda", "linear_a4", 4, 64), ("mxfp4_a6_linear_cuda", "linear_a6", 4, 64),
           ("mxfp4_a8_linear_cuda", "linear_a8", 4, 64), ("mxfp6_a6_linear_cuda", "linear_w6a6", 6, 64), ("mxfp6_a8_linear_cuda", "linear_w6a8", 6, 64),
-          ("mxfp8_a8_linear_cuda", "linear_w8a8", 8, 64))
+          ("mxfp8_a8_linear_cuda", "linear_w8a8", 8, 64), ("mxfp6_linear_cuda", "linear_w6", 6, 32))
 # (extension, name in the listing, bits per weight code, tile width knob or None)
 GROUPED = (("mxfp4_experts_cuda", "experts", 4, None), ("mxfp4_experts_a4_cuda", "experts_a4", 4, None),
            ("mxfp4_experts_a6_cuda", "experts_a6", 4, "BIE_MXFP4_MOE_A6_WN"), ("mxfp4_experts_a8_cuda", "experts_a8", 4, None),
-           ("mxfp6_experts_a6_cuda", "experts_w6a6", 6, "BIE_MXFP6_MOE_A6_WN"), ("mxfp6_experts_a8_cuda", "experts_w6a8", 6, None))
+           ("mxfp6_experts_a6_cuda", "experts_w6a6", 6, "BIE_MXFP6_MOE_A6_WN"), ("mxfp6_experts_a8_cuda", "experts_w6a8", 6, None),
+           ("mxfp6_experts_cuda", "experts_w6", 6, None))
+GRAD = ((96, 33), (2880, 2880))  # K, N
+GRAD_M = (1, 129, 300)
+GRAD_T = (1, 17, 300)
 ROUTED_T = (1, 17)  # the gemm entry at form 0, at EXPERTS[0]'s shape
 # the strip width knob of the routed decode form, for the layers that have one
 STRIP = {"experts_a4": "BIE_MXFP4_MOE_A4_STRIP", "experts_a8": "BIE_MXFP4_MOE_A8_STRIP", "experts_w6a8": "BIE_MXFP6_MOE_A8_STRIP"}
@@ -139,6 +146,8 @@ def routed(E, S, K, N, Ts):
                 for b, bname in ((None, "nobias"), (bias, "bias")):
                     for mod, name, bits, _ in GROUPED[1:]:
                         m = ext(mod)
+                        if not hasattr(m, "gemm"):
+                            continue  # a weight-only layer: no quantised activations
                         xq = m.quantize_act(xs[xpp].reshape(-1, K))
                         tail = f"{dname} {bname} E={E} S={S} K={K} N={N} T={T} xpp={xpp} form=0"
                         print(f"{name} gemm {tail} {sha(m.gemm(*xq, idx, q[bits], s, b, e_col, dtype=dt, form=0))}")
@@ -148,6 +157,32 @@ def routed(E, S, K, N, Ts):
                                 print(f"{name} strip={strip} forward {tail} {sha(m.forward(xs[xpp], idx, q[bits], s, b, e_col, form=0))}")
                                 print(f"{name} strip={strip} gemm {tail} {sha(m.gemm(*xq, idx, q[bits], s, b, e_col, dtype=dt, form=0))}")
                             del os.environ[STRIP[name]]
+
+
+def sha_any(t):
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()  # gx in the dtype or in fp32
+
+
+def grads(K, N):
+    """The four input-gradient entries; every draw from streams seeded here alone."""
+    E, S = 3, 4
+    rng = np.random.default_rng(7000 + K + N)
+    q = {4: codes(rng, E * N, K, 4), 6: codes(rng, E * N, K, 6)}
+    s = torch.from_numpy(rng.integers(118, 131, (E * N, K // 32), dtype=np.uint8)).to(DEV)
+    for dt, dname in DTS:
+        for M in GRAD_M:
+            gy = normal(rng, (M, N), dt)
+            for fmt, bits in (("mxfp4", 4), ("mxfp6", 6)):
+                gx = ext(fmt + "_linear_cuda").grad_input(gy, q[bits][:N], s[:N])
+                print(f"grad_{fmt} {dname} K={K} N={N} M={M} {sha(gx)}")
+        for T in GRAD_T:
+            idx = torch.from_numpy(rng.integers(-1, E + 1, (T, S)).astype(np.int32)).to(DEV)  # -1 and E: skipped slots
+            gy = normal(rng, (T, S, N), dt)
+            for fmt, bits in (("mxfp4", 4), ("mxfp6", 6)):
+                for odt, oname in ((None, "dtype"), (torch.float32, "fp32")):
+                    gx = ext(fmt + "_experts_cuda").grad_input(gy, idx, q[bits].reshape(E, N, -1), s.reshape(E, N, -1), out_dtype=odt)
+                    print(f"grad_experts_{fmt} {dname} gx={oname} E={E} S={S} K={K} N={N} T={T} {sha_any(gx)}")
 
 
 def main():
@@ -161,6 +196,8 @@ def main():
     for wn in (1, 2):
         grouped(E, S, K, N, Ts[-1:], knob_value=wn)
     routed(E, S, K, N, ROUTED_T)
+    for K, N in GRAD:
+        grads(K, N)
 
 
 if __name__ == "__main__":
