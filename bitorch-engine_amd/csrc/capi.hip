@@ -183,6 +183,13 @@ int mxfp8_a8_gemm_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* ro
 int mxfp8_a8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, void* workspace, long M,
                             long N, long K, int dtype, int form, hipStream_t st);
 
+// mxfp8.hip
+int mxfp8_form(long M, long N, long K, int dtype);
+bool mxfp8_decode_ok(long M);
+int mxfp8_decode_rows();
+int mxfp8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
+                         int dtype, int form, hipStream_t st);
+
 // mxfp6_a8.hip
 int mxfp6_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st);
 int mxfp6_dequant_launch(const uint8_t* qw, const uint8_t* sc, void* w, long N, long K, int dtype, hipStream_t st);
@@ -1097,7 +1104,7 @@ int bie_mxfp4_col_exp(const uint8_t* scales, uint8_t* e_col, long N, long K, voi
 
 int bie_mxfp4_form(long M, long N, long K, int dtype) { return mxfp4_form(M, N, K, dtype); }
 
-// One entry check for the weight-only layers and their input gradients (MXFP4 and MXFP6 weights against fp16 / bf16 activations; their
+// One entry check for the weight-only layers and their input gradients (MXFP4, MXFP6 and MXFP8 weights against fp16 / bf16 activations; their
 // host side is csrc/mx_w16_launch.cuh).  A row names the format's functions; the expert and gradient helpers are further down, after
 // the checks they share with the block-scaled layers.
 struct mx_w16_entry {
@@ -1115,6 +1122,8 @@ static const mx_w16_entry MX_W4A16 = {mxfp4_form,          mxfp4_decode_ok,     
                                       mxfp4_moe_decode_ok, mxfp4_moe_forward_launch, mxfp4_grad_input_launch, mxfp4_moe_grad_input_launch};
 static const mx_w16_entry MX_W6A16 = {mxfp6_form,          mxfp6_decode_ok,          mxfp6_decode_rows,       mxfp6_forward_launch,       mxfp6_moe_form,
                                       mxfp6_moe_decode_ok, mxfp6_moe_forward_launch, mxfp6_grad_input_launch, mxfp6_moe_grad_input_launch};
+// MXFP8 weights: the linear layer only (no expert layer and no input-gradient kernel)
+static const mx_w16_entry MX_W8A16 = {mxfp8_form, mxfp8_decode_ok, mxfp8_decode_rows, mxfp8_forward_launch, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 static int mx_w16_forward(const mx_w16_entry& L, const char* fn, const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                           const void* bias, void* y, long M, long N, long K, int dtype, int form, void* stream) {
@@ -1353,6 +1362,14 @@ int bie_mx8a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_
 int bie_mx8a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                    const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream) {
     return mx_dense_gemm(MX_W8A8, "bie_mx8a8_gemm", xq, xs, row_flag, qweight, scales, e_col, bias, y, workspace, M, N, K, dtype, form, stream);
+}
+
+// ---- MXFP8 weight-only (W8A16): the W8A8 layer's qweight / scales against fp16 / bf16 activations.  The checks are the MXFP6 entry's.
+int bie_mx8_form(long M, long N, long K, int dtype) { return mxfp8_form(M, N, K, dtype); }
+
+int bie_mx8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                           long N, long K, int dtype, int form, void* stream) {
+    return mx_w16_forward(MX_W8A16, "bie_mx8_linear_forward", x, qweight, scales, e_col, bias, y, M, N, K, dtype, form, stream);
 }
 
 // ---- MXFP6 weight-only (W6A16).  Everything is checked here, before any device call; the shape limits are the MXFP4 layer's.

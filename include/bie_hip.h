@@ -1062,6 +1062,27 @@ int bie_mx8a8_linear_forward(const void* x, const uint8_t* qweight, const uint8_
 int bie_mx8a8_gemm(const uint8_t* xq, const uint8_t* xs, const uint8_t* row_flag, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                    const void* bias, void* y, void* workspace, long M, long N, long K, int dtype, int form, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mxfp8 (w8a16)
+ * MXFP8 weights (the mxfp8 w8a8 section's qweight / scales, byte for byte) against fp16 / bf16 activations that are left alone: the
+ * mxfp6 (w6a16) section's contract with E4M3 elements (MXFP8LinearCuda; INTEGRATION.md, "MXFP8 linear layer").  The semantics are
+ * defined by this library:
+ *   W[n, k]  = e4m3(qweight[n, k]) * 2^(scales[n, k/32] - 127)   (exact in fp32)
+ *   y[m, n]  = dt( sum_k x[m, k] * W[n, k] + bias[n] ): products exact, the sum in fp32 in any order, one rounding to the dtype (0=f16 1=bf16)
+ *   K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1.  A column n with a scale-255 block is NaN in every row; a scale-0 block is 2^-127 and
+ *   may flush to zero; a NaN code (0x7F / 0xFF) in row n of qweight makes y[:, n] NaN and leaves the other columns alone.  Non-finite
+ *   x goes through the products by IEEE rules; no row affects another row.
+ * bie_mx8_form: 0 = decode form (exists for M <= 32), 1 = prefill form (MFMA GEMM).  The plan takes the decode form for M <= 32;
+ *   BIE_MXFP8_FORM=0/1 forces one (0 only where the decode form exists).  Host only.
+ * bie_mx8_linear_forward: x [M, K] and qweight (16-byte aligned), bias [N] in the dtype or NULL, y [M, N]; e_col of bie_mxfp4_col_exp (the
+ *   prefill form reads it; the decode form takes NULL); form -1 = bie_mx8_form.  The decode form keeps the fp32 range of W; the prefill
+ *   form holds e4m3 * 2^(s - e_col[n]) in 16 bits, so within a column a weight keeps 2^-24 (fp16 subnormal step) of its column's
+ *   largest scale.  Form 0 with M > 32: BIE_ERR_UNSUPPORTED.
+ * Argument order and return codes are bie_mxfp6_linear_forward's.  Every argument is validated on the host before any device call;
+ * nothing allocates or synchronises with the host (graph-capturable). */
+int bie_mx8_form(long M, long N, long K, int dtype);
+int bie_mx8_linear_forward(const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias, void* y, long M,
+                           long N, long K, int dtype, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
