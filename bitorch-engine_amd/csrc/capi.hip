@@ -189,6 +189,11 @@ bool mxfp8_decode_ok(long M);
 int mxfp8_decode_rows();
 int mxfp8_forward_launch(const void* x, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y, long M, long N, long K,
                          int dtype, int form, hipStream_t st);
+// mxfp8_moe.hip
+int mxfp8_moe_form(long P, long E, long N, long K, int dtype);
+bool mxfp8_moe_decode_ok(long P);
+int mxfp8_moe_forward_launch(const void* x, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* ecol, const void* bias, void* y,
+                             void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, hipStream_t st);
 
 // mxfp6_a8.hip
 int mxfp6_quantize_launch(const void* w, uint8_t* qw, uint8_t* sc, long N, long K, int dtype, hipStream_t st);
@@ -1122,8 +1127,9 @@ static const mx_w16_entry MX_W4A16 = {mxfp4_form,          mxfp4_decode_ok,     
                                       mxfp4_moe_decode_ok, mxfp4_moe_forward_launch, mxfp4_grad_input_launch, mxfp4_moe_grad_input_launch};
 static const mx_w16_entry MX_W6A16 = {mxfp6_form,          mxfp6_decode_ok,          mxfp6_decode_rows,       mxfp6_forward_launch,       mxfp6_moe_form,
                                       mxfp6_moe_decode_ok, mxfp6_moe_forward_launch, mxfp6_grad_input_launch, mxfp6_moe_grad_input_launch};
-// MXFP8 weights: the linear layer only (no expert layer and no input-gradient kernel)
-static const mx_w16_entry MX_W8A16 = {mxfp8_form, mxfp8_decode_ok, mxfp8_decode_rows, mxfp8_forward_launch, nullptr, nullptr, nullptr, nullptr, nullptr};
+// MXFP8 weights: the linear and the expert layer (no input-gradient kernel)
+static const mx_w16_entry MX_W8A16 = {mxfp8_form,          mxfp8_decode_ok,          mxfp8_decode_rows, mxfp8_forward_launch, mxfp8_moe_form,
+                                      mxfp8_moe_decode_ok, mxfp8_moe_forward_launch, nullptr,           nullptr};
 
 static int mx_w16_forward(const mx_w16_entry& L, const char* fn, const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                           const void* bias, void* y, long M, long N, long K, int dtype, int form, void* stream) {
@@ -1422,6 +1428,14 @@ static int mx_w16_moe_forward(const mx_w16_entry& L, const char* fn, const void*
 int bie_mxfp4_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
                           void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
     return mx_w16_moe_forward(MX_W4A16, "bie_mxfp4_moe_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
+}
+
+// ---- MXFP8 weight-only (W8A16) mixture of experts: the MXFP4 layer's entry check, the workspace bie_mxfp4_moe_workspace_bytes.
+int bie_mx8_moe_form(long P, long E, long N, long K, int dtype) { return mxfp8_moe_form(P, E, N, K, dtype); }
+
+int bie_mx8_moe_forward(const void* x, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col, const void* bias,
+                        void* y, void* workspace, long T, long S, long E, long N, long K, int x_per_pair, int dtype, int form, void* stream) {
+    return mx_w16_moe_forward(MX_W8A16, "bie_mx8_moe_forward", x, idx, qweight, scales, e_col, bias, y, workspace, T, S, E, N, K, x_per_pair, dtype, form, stream);
 }
 
 // ---- MXFP6 weight-only (W6A16) mixture of experts: the MXFP4 layer's entry check, the workspace bie_mxfp4_moe_workspace_bytes.

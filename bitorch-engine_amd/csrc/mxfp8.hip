@@ -40,8 +40,6 @@
 namespace bie {
 
 // ---- decode form --------------------------------------------------------------------------------------------------------------------
-constexpr int MX8_UNIT = 16;  // bytes (= weights) per unit of work: 16 (half a block) or 32 (a block)
-
 // Workgroup: columns C * blockIdx.x .. + C - 1, C = CT * 256 / G (clamped reads past N, never stored), rows 0 .. M - 1 (M <= R).  Group
 // g = t / G holds columns g CT .. + CT - 1 of those; its thread j = t % G takes the units j, j + G, ... of K.
 template <int DT, int R, int CT, int G>

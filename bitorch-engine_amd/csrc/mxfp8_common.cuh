@@ -35,6 +35,9 @@ __device__ __forceinline__ typename mx_frag<DT>::t mx8_frag(uint32_t w0, uint32_
     return typename mx_frag<DT>::t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
+// the decode forms (mx8_decode_kernel of mxfp8.hip, mx8m_decode_kernel of mxfp8_moe.hip)
+constexpr int MX8_UNIT = 16;  // bytes (= weights) per unit of work: 16 (half a block) or 32 (a block)
+
 // ---- the weight-only (W8A16) prefill tile ----------------------------------------------------------------------------------------------------
 constexpr int MX8_BK = 64;  // k per stage: two blocks, 64 code bytes per weight row
 // 64 bytes per weight row in LDS, NO pad: the 16-byte piece c (0 .. 3) of tile row n is stored at piece c ^ ((n >> 2) & 3) of the row, so
