@@ -186,6 +186,8 @@ SIGNATURES = {
     "bie_mx8_linear_forward": (_i, [_vp] * 6 + [_l] * 3 + [_i, _i, _vp]),
     "bie_mx8_moe_form": (_i, [_l] * 4 + [_i]),
     "bie_mx8_moe_forward": (_i, [_vp] * 8 + [_l] * 5 + [_i, _i, _i, _vp]),
+    "bie_mx8_linear_grad_input": (_i, [_vp] * 5 + [_l] * 3 + [_i, _vp]),
+    "bie_mx8_moe_grad_input": (_i, [_vp] * 7 + [_l] * 5 + [_i, _i, _vp]),
 }
 
 

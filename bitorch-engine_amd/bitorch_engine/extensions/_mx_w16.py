@@ -1,5 +1,6 @@
 """The forward / grad_input wrappers of the weight-only MX layers (MXFP4, MXFP6 and MXFP8 weights against fp16 / bf16 activations), written
-once: the linear modules (the MXFP8 one has no grad_input and passes blk_exp = None), the two experts modules and the input gradients that the MXFP6 `_a8` modules define call the same four
+once: the linear modules, the experts modules and the input gradients (those that the MXFP6 `_a8` modules define, and mxfp8_grad_cuda's for
+the MXFP8 weights: the two MXFP8 layer modules define none and pass blk_exp = None) call the same four
 sequences of checks, allocations and one C entry, and differ in the `bie_` symbol stem, the prefix of their messages, the function that
 reads (N, K) or (E, N, K) off the weights and the col_exp / blk_exp they fill a missing e_col / e_blk with.  A module states those in a
 Dense or an Experts object and keeps its own `forward` and `grad_input` definitions (names, argument names, defaults and docstrings are

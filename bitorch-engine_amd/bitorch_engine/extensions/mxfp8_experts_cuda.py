@@ -7,9 +7,10 @@ are this library's own (include/bie_hip.h, INTEGRATION.md "MXFP8 W8A16 mixture-o
   y[t, s] = dt( x_row . W[idx[t, s]]^T + bias[idx[t, s]] ),  +0 for a skipped slot;   x_row = x[t] (x [T, K]) or x[t, s] (x [T, S, K])
 
 Products are exact, the sum is in fp32 and there is one rounding.  quantize / dequant are mxfp8_a8_linear_cuda's on the [E * N, K] view
-(the format is row-wise) and col_exp is mxfp4_experts_cuda's (the same object: the scales are the same bytes).  There is no
-packed-weight input gradient for MXFP8.  Nothing here synchronises with the host (the routing is read on the device), so every entry
-can be captured in a graph."""
+(the format is row-wise) and col_exp is mxfp4_experts_cuda's (the same object: the scales are the same bytes).  The packed-weight
+input gradient of this format (gx[p] = gy[p] . W[idx[p]], csrc/mxfp8_grad.hip) is mxfp8_grad_cuda's experts_grad_input, with its
+experts_blk_exp; this module's surface has neither.  Nothing here synchronises with the host (the routing is read on the device), so
+every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip

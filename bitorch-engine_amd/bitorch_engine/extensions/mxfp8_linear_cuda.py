@@ -6,8 +6,9 @@ format and the arithmetic are this library's own (include/bie_hip.h, INTEGRATION
   y = dt( x . W^T + bias )  (products exact, fp32 sums, one rounding)
 
 qweight and scales are byte for byte those of mxfp8_a8_linear_cuda, so quantize and dequant are that module's, and col_exp the MXFP4
-one (the scale bytes are the same).  forward runs the layer (the form from bie_mx8_form unless one is given).  There is no
-packed-weight input gradient for MXFP8.  Nothing here synchronises with the host, so every entry can be captured in a graph."""
+one (the scale bytes are the same).  forward runs the layer (the form from bie_mx8_form unless one is given).  The packed-weight
+input gradient of this format (gx = gy . W, csrc/mxfp8_grad.hip) is mxfp8_grad_cuda's grad_input, with its blk_exp; this module's
+surface has neither.  Nothing here synchronises with the host, so every entry can be captured in a graph."""
 import torch
 
 from bitorch_engine import _hip

@@ -9,10 +9,13 @@ Products are exact, the sum is in fp32 and there is one rounding: MXFP8LinearCud
 scales uint8 [E, N, K/32] are MXFP8LinearCuda's format per expert; e_col is derived from scales and not saved.  A stacked MXFP4 state
 dict (qweight [E, N, K/2]) and an MXFP6 one ([E, N, 3K/4]) are refused: the codes are a different format, not a different packing.
 
-The surface is MXFP6ExpertsLinearCuda's without the grad_input argument: there is no packed-weight input gradient for MXFP8, so grad_x
-comes from an fp32 image of every expert's W.  Training (train() with the latent weight): re-quantised on every call, the forward runs
-on the kernels and the backward is the straight-through composition in torch, expert by expert, with grad_weight = gy^T . x at the
-UNQUANTISED x (the weight-only rule).  Eval: the packed weight; a forward with grad enabled is differentiable in x (and bias)."""
+The surface is MXFP6ExpertsLinearCuda's without the grad_input constructor argument.  Training (train() with the latent weight):
+re-quantised on every call, the forward runs on the kernels and the backward is the straight-through composition in torch, expert by
+expert, with grad_weight = gy^T . x at the UNQUANTISED x (the weight-only rule).  Eval: the packed weight; a forward with grad enabled
+is differentiable in x (and bias).  The attribute grad_input (not a constructor argument, not saved) chooses where grad_x comes from:
+"torch" (the default) builds an fp32 image of every expert's W and loops over the experts on the host; "kernel" takes it from the
+packed weights in one grouped call (csrc/mxfp8_grad.hip, extensions/mxfp8_grad_cuda.py: nothing is dequantised, and with frozen weights
+and no bias gradient the backward has no expert loop and no host synchronisation, so it can be captured in a graph)."""
 import math
 import typing
 
@@ -23,7 +26,10 @@ from torch.autograd import Function
 from bitorch_engine.utils.safe_import import import_extension
 from bitorch_engine.layers.qlinear.ternary.layer import TernaryWeightState
 
+from bitorch_engine.layers.qlinear.nbit.cuda.mxfp8_layer import _checked_grad_input
+
 mxfp8_experts_cuda = import_extension("mxfp8_experts_cuda")
+mxfp8_grad_cuda = import_extension("mxfp8_grad_cuda")
 
 
 class MXFP8ExpertsLinearForward(Function):
@@ -32,11 +38,13 @@ class MXFP8ExpertsLinearForward(Function):
       grad_x[row(p)] += gy[p] . W[e]        (summed over a token's slots when x is [T, K])
       grad_weight[e]  = gy[pairs of e]^T . x_rows
       grad_bias[e]    = sum gy[pairs of e]
-    Skipped slots contribute nothing."""
+    Skipped slots contribute nothing.  With kernel=True grad_x is one call of mxfp8_grad_cuda.experts_grad_input on the packed weights
+    (fp32 rows summed over a token's slots and rounded once when x is [T, K]), and the loop runs for grad_weight / grad_bias only."""
 
     @staticmethod
-    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, idx, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, idx, qweight, scales)
+        ctx.kernel = kernel
         return mxfp8_experts_cuda.forward(x, idx, qweight, scales, bias, e_col)
 
     @staticmethod
@@ -46,6 +54,15 @@ class MXFP8ExpertsLinearForward(Function):
         E, N, K = scales.shape[0], scales.shape[1], scales.shape[2] * 32
         T, S = idx.shape
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gxk = None
+        if need_x and ctx.kernel:
+            if x.dim() == 3:
+                gxk = mxfp8_grad_cuda.experts_grad_input(gy, idx, qweight, scales).reshape(T, S, K)
+            else:
+                gxk = mxfp8_grad_cuda.experts_grad_input(gy, idx, qweight, scales, out_dtype=torch.float32).reshape(T, S, K).sum(1).to(gy.dtype)
+            need_x = False
+            if not (need_w or need_b):
+                return gxk, None, None, None, None, None, None, None
         g = gy.reshape(T * S, N).float()
         flat = idx.reshape(-1).long()
         xr = (x if x.dim() == 3 else x[:, None, :].expand(T, S, K)).reshape(T * S, K).float()
@@ -66,13 +83,26 @@ class MXFP8ExpertsLinearForward(Function):
                 gb[e] = ge.sum(0)
         if need_x:
             gx = (gx.reshape(T, S, K) if x.dim() == 3 else gx.reshape(T, S, K).sum(1)).to(gy.dtype)
-        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None
+        elif gxk is not None:
+            gx = gxk
+        return gx, None, None if gw is None else gw.to(gy.dtype), None if gb is None else gb.to(gy.dtype), None, None, None, None
 
 
 class MXFP8ExpertsLinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [E, N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight),
     the e4m3fn codes `qweight` uint8 [E, N, K] and E8M0 `scales` uint8 [E, N, K/32] (buffers), an optional `bias` [E, N].
-    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16."""
+    K % 32 == 0, K <= 2^20; 1 <= E <= 1024; dtype fp16 or bf16.  grad_input: "torch" or "kernel", an attribute of the object only (the
+    module docstring)."""
+
+    _grad_input = "torch"
+
+    @property
+    def grad_input(self) -> str:
+        return self._grad_input
+
+    @grad_input.setter
+    def grad_input(self, value: str) -> None:
+        self._grad_input = _checked_grad_input(value)
 
     def __init__(self, num_experts: int, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
                  dtype: torch.dtype = torch.float16) -> None:
@@ -161,4 +191,5 @@ class MXFP8ExpertsLinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return mxfp8_experts_cuda.forward(x, idx, qweight, scales, self.bias, e_col)
-        return MXFP8ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col)
+        return MXFP8ExpertsLinearForward.apply(x, idx, self.weight if training else None, self.bias, qweight, scales, e_col,
+                                               self.grad_input == "kernel")

@@ -10,8 +10,9 @@ format, not a different packing.
 
 Training (train() with the latent weight): re-quantised on every call by the OCP MX rule, the forward runs on the kernels and the
 backward is the straight-through composition in torch.  Eval: the packed qweight / scales; a forward with grad enabled is
-differentiable in x (and bias).  There is no packed-weight input gradient for MXFP8, so the class takes no grad_input argument: grad_x
-comes from an fp32 image of W."""
+differentiable in x (and bias).  The attribute grad_input (not a constructor argument, not saved) chooses where grad_x comes from: "torch"
+(the default) builds an fp32 image of W on every backward call; "kernel" takes it from the packed weight in one call
+(csrc/mxfp8_grad.hip, extensions/mxfp8_grad_cuda.py: no image of W is built).  grad_weight and grad_bias are the same in both."""
 import math
 import typing
 
@@ -24,17 +25,25 @@ from bitorch_engine.utils.model_helper import flatten_x, unflatten_x
 from bitorch_engine.layers.qlinear.ternary.layer import TernaryWeightState
 
 mxfp8_linear_cuda = import_extension("mxfp8_linear_cuda")
+mxfp8_grad_cuda = import_extension("mxfp8_grad_cuda")
+
+
+def _checked_grad_input(value):
+    if value not in ("torch", "kernel"):
+        raise ValueError(f'grad_input must be "torch" or "kernel" (got {value!r})')
+    return value
 
 
 class MXFP8LinearForward(Function):
     """Forward: the layer kernels.  Backward (straight-through estimator, in fp32, cast to the dtype):
-      grad_x      = gy . W            (W dequantised to fp32)
+      grad_x      = gy . W            (W dequantised to fp32; with kernel=True one call of mxfp8_grad_cuda.grad_input on the packed weight)
       grad_weight = gy^T . x          (the float latent weight, as if it were W)
       grad_bias   = sum_m gy"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, qweight, scales, e_col):
+    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False):
         ctx.save_for_backward(x, qweight, scales)
+        ctx.kernel = kernel
         return mxfp8_linear_cuda.forward(x, qweight, scales, bias, e_col)
 
     @staticmethod
@@ -43,18 +52,32 @@ class MXFP8LinearForward(Function):
         x, qweight, scales = ctx.saved_tensors
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
-            grad_x = gy.float().mm(mxfp8_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
+            if ctx.kernel:
+                grad_x = mxfp8_grad_cuda.grad_input(gy, qweight, scales)
+            else:
+                grad_x = gy.float().mm(mxfp8_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
         if ctx.needs_input_grad[1]:
             grad_w = gy.float().t().mm(x.float()).to(gy.dtype)
         if ctx.needs_input_grad[2]:
             grad_b = gy.float().sum(0).to(gy.dtype)
-        return grad_x, grad_w, grad_b, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None
 
 
 class MXFP8LinearCuda(TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight), the
     e4m3fn codes `qweight` uint8 [N, K] and E8M0 `scales` uint8 [N, K/32] (buffers), an optional `bias` [N].
-    K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16."""
+    K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16.  grad_input: "torch" or "kernel", an attribute of the object only (the module
+    docstring)."""
+
+    _grad_input = "torch"
+
+    @property
+    def grad_input(self) -> str:
+        return self._grad_input
+
+    @grad_input.setter
+    def grad_input(self, value: str) -> None:
+        self._grad_input = _checked_grad_input(value)
 
     def __init__(self, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
                  dtype: torch.dtype = torch.float16) -> None:
@@ -139,5 +162,5 @@ class MXFP8LinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return unflatten_x(mxfp8_linear_cuda.forward(x2, qweight, scales, self.bias, e_col), lead)
-        out = MXFP8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col)
+        out = MXFP8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel")
         return unflatten_x(out, lead)

@@ -286,6 +286,11 @@ int mxfp6_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc
                             hipStream_t st);
 int mxfp6_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
                                 long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st);
+// mxfp8_grad.hip
+int mxfp8_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, long M, long N, long K, int dtype,
+                            hipStream_t st);
+int mxfp8_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
+                                long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -1127,9 +1132,9 @@ static const mx_w16_entry MX_W4A16 = {mxfp4_form,          mxfp4_decode_ok,     
                                       mxfp4_moe_decode_ok, mxfp4_moe_forward_launch, mxfp4_grad_input_launch, mxfp4_moe_grad_input_launch};
 static const mx_w16_entry MX_W6A16 = {mxfp6_form,          mxfp6_decode_ok,          mxfp6_decode_rows,       mxfp6_forward_launch,       mxfp6_moe_form,
                                       mxfp6_moe_decode_ok, mxfp6_moe_forward_launch, mxfp6_grad_input_launch, mxfp6_moe_grad_input_launch};
-// MXFP8 weights: the linear and the expert layer (no input-gradient kernel)
-static const mx_w16_entry MX_W8A16 = {mxfp8_form,          mxfp8_decode_ok,          mxfp8_decode_rows, mxfp8_forward_launch, mxfp8_moe_form,
-                                      mxfp8_moe_decode_ok, mxfp8_moe_forward_launch, nullptr,           nullptr};
+// MXFP8 weights: the linear and the expert layer, and their input gradient (mxfp8_grad.hip)
+static const mx_w16_entry MX_W8A16 = {mxfp8_form,          mxfp8_decode_ok,          mxfp8_decode_rows,       mxfp8_forward_launch,       mxfp8_moe_form,
+                                      mxfp8_moe_decode_ok, mxfp8_moe_forward_launch, mxfp8_grad_input_launch, mxfp8_moe_grad_input_launch};
 
 static int mx_w16_forward(const mx_w16_entry& L, const char* fn, const void* x, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_col,
                           const void* bias, void* y, long M, long N, long K, int dtype, int form, void* stream) {
@@ -1685,6 +1690,17 @@ int bie_mxfp6_linear_grad_input(const void* gy, const uint8_t* qweight, const ui
 int bie_mxfp6_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                              void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
     return mx_w16_moe_grad_input(MX_W6A16, "bie_mxfp6_moe_grad_input", gy, idx, qweight, scales, e_blk, gx, workspace, T, S, E, N, K, dtype, out_fp32, stream);
+}
+
+// ---- MXFP8 input gradient: the same checks on the MXFP8 weight format (bie_mxfp4_blk_exp serves it too).
+int bie_mx8_linear_grad_input(const void* gy, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx, long M, long N, long K,
+                              int dtype, void* stream) {
+    return mx_w16_grad_input(MX_W8A16, "bie_mx8_linear_grad_input", gy, qweight, scales, e_blk, gx, M, N, K, dtype, stream);
+}
+
+int bie_mx8_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
+                           void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
+    return mx_w16_moe_grad_input(MX_W8A16, "bie_mx8_moe_grad_input", gy, idx, qweight, scales, e_blk, gx, workspace, T, S, E, N, K, dtype, out_fp32, stream);
 }
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.

@@ -1,6 +1,6 @@
 // The host side of the weight-only MX layers (MXFP4, MXFP6 and MXFP8 weights against fp16 / bf16 activations), written once: the plan and the
 // launchers of the linear layers (mxfp4.hip, mxfp6.hip, mxfp8.hip), the expert layers (mxfp4_moe.hip, mxfp6_moe.hip, mxfp8_moe.hip) and the input gradients
-// (mxfp4_grad.hip, mxfp6_grad.hip).  A .hip file keeps its kernels and measured constants and names them in a small traits type; its
+// (mxfp4_grad.hip, mxfp6_grad.hip, mxfp8_grad.hip).  A .hip file keeps its kernels and measured constants and names them in a small traits type; its
 // mxfp*_ symbols are one call each of the templates below.  The arrangement, and why a knob's name reaches BIE_KNOB as a static member
 // of the layer's type (every layer keeps its own once-per-process cache), are those of mx_scaled_launch.cuh.
 #pragma once

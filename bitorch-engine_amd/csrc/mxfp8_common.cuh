@@ -1,5 +1,6 @@
 // The MXFP8 (OCP microscaling FP8, E4M3 elements) weight-only (W8A16) device-side rules (gfx950): the two-at-a-time convert of code bytes
-// to exact 16-bit values and the 128 x 128 prefill tile body (mx8_gemm_tile: mx8_gemm_kernel of mxfp8.hip).  The E8M0 block scales, the
+// to exact 16-bit values, the 128 x 128 prefill tile body (mx8_gemm_tile: mx8_gemm_kernel of mxfp8.hip) and the input-gradient 128 x 128
+// tile body (mx8_dgrad_tile: the kernels of mxfp8_grad.hip).  The E8M0 block scales, the
 // rebias, the row sources, the x side of the tile and the 16-bit MFMA are those of mxfp4_common.cuh; the half-wave sum and the decode
 // forms' group dispatch are those of mxfp6_common.cuh.
 //
@@ -191,6 +192,188 @@ __device__ __forceinline__ void mx8_gemm_tile(const Rows& rows, const uint16_t* 
                 }
             }
     }
+}
+
+// ---- the input-gradient tile -----------------------------------------------------------------------------------------------------------------
+constexpr int MX8_DG_BM = 128, MX8_DG_BK = 128, MX8_DG_BN = 64;  // rows of gy, columns k of gx, contraction rows n of a stage
+constexpr int MX8_DG_APITCH = MX8_DG_BN * 2 + 16;                // bytes per gy row in LDS (MX_APITCH's pad)
+// The codes of a stage in LDS: [64 k pairs][64 n] of 16-bit units (unit (p, n) = the code bytes of W[n, 2 p] and W[n, 2 p + 1]), 128
+// bytes per k pair + 16: the 16-byte slot (address / 16) of the chunk of rows 8 c .. + 7 of k pair p is 9 p + c.  By the bank rule of
+// mxfp6_common.cuh (bank = dword mod 64; a ds_read_b128 is served per 16 lanes, a ds_write_b128 per 8 consecutive lanes on bank mod 32):
+//   fragment reads (ds_read_b128): the lanes of a half-wave read ONE chunk c of the k pairs p = p0 + r, r = 0 .. 31.  The slot mod 16 is
+//     (9 r + const) mod 16, one-to-one on r mod 16 (9 is odd), so any 16 lanes whose r differ mod 16 (each of the two 16-lane groups of a
+//     half-wave, whichever lanes they are) cover all 16 slots = all 64 banks once: no conflict.
+//   staging writes (ds_write_b128): the 8 lanes hold the dword columns d = 4 a + i (i = 0 .. 3: k pairs p = 2 d + j in write j) of the
+//     chunks c = 2 b and 2 b + 1; slot mod 8 = (9 (8 a + 2 i + j) + c) mod 8 = (2 i + (c & 1) + j + 2 b) mod 8: 8 distinct values for
+//     the 8 (i, c & 1), no conflict.
+// A pitch of 128 cannot do the reads (slot = 8 p + c: two values mod 16), and 128 + 8 is not 16-byte aligned.
+constexpr int MX8_DG_WPITCH = MX8_DG_BN * 2 + 16;
+constexpr int MX8_DG_SPITCH = MX8_DG_BN + 4;  // fp32 per block-column of rebiased scales (MX_DG_SPITCH's pad)
+constexpr int MX8_DG_STAGE = MX8_DG_BM * MX8_DG_APITCH + (MX8_DG_BK / 2) * MX8_DG_WPITCH + (MX8_DG_BK / 32) * MX8_DG_SPITCH * 4;  // 18432 + 9216 + 1088
+static_assert(2 * MX8_DG_STAGE + MXM_BM * 4 <= 65536, "two buffers and the grouped kernel's prow[] in the 64 KiB of static LDS");
+
+// Four dwords of one k pair (dword i: the unit of row n + 2 i in the low half, of row n + 2 i + 1 in the high half) at their rows' rebiased
+// scales -> the 8-n fragments of the units' first bytes (column 2 p) and second bytes (column 2 p + 1): one convert per unit, each half
+// of a dword under its own row's scale (op_sel), the halves of the results regrouped.
+template <int DT>
+__device__ __forceinline__ void mx8_frag_columns(const uint4_t& w, const float4_t& s0, const float4_t& s1, typename mx_frag<DT>::t& lo,
+                                                 typename mx_frag<DT>::t& hi) {
+    typedef mx8_w16<DT> C;
+    const typename C::t v0 = C::template cvt<false>(w.x, s0[0]), v1 = C::template cvt<true>(w.x, s0[1]);
+    const typename C::t v2 = C::template cvt<false>(w.y, s0[2]), v3 = C::template cvt<true>(w.y, s0[3]);
+    const typename C::t v4 = C::template cvt<false>(w.z, s1[0]), v5 = C::template cvt<true>(w.z, s1[1]);
+    const typename C::t v6 = C::template cvt<false>(w.w, s1[2]), v7 = C::template cvt<true>(w.w, s1[3]);
+    lo = typename mx_frag<DT>::t{v0[0], v1[0], v2[0], v3[0], v4[0], v5[0], v6[0], v7[0]};
+    hi = typename mx_frag<DT>::t{v0[1], v1[1], v2[1], v3[1], v4[1], v5[1], v6[1], v7[1]};
+}
+
+// One 128 x 128 tile of gx = gy . W on v_mfma_f32_32x32x16_{bf16,f16}, contracted over the N MXFP8 weight rows that start at row r0 of
+// qw / sc (0, or (long)e * N for expert e): mx_dgrad_tile's contract (mxfp4_common.cuh) with E4M3 elements.  Tile rows from `rows` (a
+// live row reads gy[src] and writes gx[dst]), columns k0 .. of K, rebiased by eblk[k / 32] (the caller's pointer already at the
+// expert's K / 32 codes).  ODT, the element type of gx, is DT or BIE_F32.  4 waves as 2 x 2, wave tile 64 x 64.
+// Per stage of 64 n a thread loads 4 x 16 bytes of gy, eight dwords of codes (dword column d of the tile's 32: k pairs 2 d, 2 d + 1; rows
+// 8 c .. + 7 of the stage) and one scale byte into registers while the MFMAs run on the other LDS buffer.  A wave's code load touches
+// four rows, the 128 contiguous bytes of each (lane bits 0, 1, 3, 4, 5 are d; bit 2 and the wave are c).  It then regroups the eight
+// dwords with eight v_perm_b32 (the low 16-bit units of two rows into one dword, the high units into another) and writes two
+// ds_write_b128: LDS holds [k pair][n], unit (p, n) next to (p, n + 1).  The scale is rebiased to fp32 and staged as [block-column][n]
+// (mx_dgrad_tile's).  Lane (r = lane & 31, h = lane >> 5) of a 16-n step reads the 8 units of k pair r, rows 8 h .. + 7, in one
+// ds_read_b128 and their 8 scales in two; each unit is one v_cvt_scalef32_pk_{f16,bf16}_fp8 at its own row's scale; the 8 first values
+// and the 8 second values are the B fragments of two MFMAs whose output column for lane r is k0 + 2 r and k0 + 2 r + 1, so the epilogue
+// stores two adjacent columns per lane.  No 16-bit image of W, in LDS or anywhere.  gy rows have any length N: whole 16-byte pieces
+// where `vec` (N % 8 == 0 and gy 16-byte aligned), else 16-bit loads, each guarded by n < N.  Dead rows and whatever lies past N / K:
+// gy and codes count as zero and scales as 1.0, so the padding adds exact zeros; the code and scale loads are clamped to the last row /
+// column and their values replaced, not skipped.  All 256 threads of the workgroup must call it together.
+template <int DT, int ODT, class Rows>
+__device__ __forceinline__ void mx8_dgrad_tile(const Rows& rows, const uint16_t* __restrict__ gy, const uint8_t* __restrict__ qw,
+                                               const uint8_t* __restrict__ sc, const uint8_t* __restrict__ eblk, void* __restrict__ gx, long r0,
+                                               int k0, int N, int K, bool vec) {
+    typedef mx_frag<DT> F;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * MX8_DG_STAGE];
+    constexpr int B_OFF = MX8_DG_BM * MX8_DG_APITCH, S_OFF = B_OFF + (MX8_DG_BK / 2) * MX8_DG_WPITCH;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wy = wave >> 1, wx = wave & 1;
+    const int NT = (N + MX8_DG_BN - 1) / MX8_DG_BN, KB = K >> 5;
+
+    // this thread's load slots
+    const int bd = (t & 3) | (((t >> 3) & 7) << 2), bc = ((t >> 2) & 1) | (wave << 1);  // codes: dword column bd, rows 8 bc .. + 7 of the stage
+    const bool bk_ok = k0 + bd * 4 < K;
+    const uint32_t wcol = (uint32_t)min(k0 + bd * 4, K - 4);
+    uint32_t woff[8];  // the eight rows' byte offsets from the stage's first row (below 64 K <= 2^26): loop-invariant in a whole stage
+#pragma unroll
+    for (int i = 0; i < 8; i++) woff[i] = (uint32_t)(bc * 8 + i) * (uint32_t)K + wcol;
+    const int sn = t >> 2, sb = t & 3;  // scale: row sn of the stage, block-column sb of the tile
+    const bool sb_ok = (k0 >> 5) + sb < KB;
+    const uint8_t* ssrc = sc + r0 * KB + min((k0 >> 5) + sb, KB - 1);
+    const uint32_t eb = eblk[min((k0 >> 5) + sb, KB - 1)];
+    const uint16_t* grow[4];  // the gy rows of this thread's four 16-byte pieces per stage: tile row (t + 256 i) / 8, piece t & 7
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = (t + 256 * i) >> 3;
+        grow[i] = rows.live(row) ? gy + rows.src(row) * N : nullptr;
+    }
+    uint4_t ra[4];
+    uint32_t rb[8];
+    float rs;
+    auto load = [&](int nt) {
+        const int na = nt * MX8_DG_BN + (t & 7) * 8;  // the first n of this thread's pieces
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (!grow[i] || na >= N) {
+                ra[i] = uint4_t{0u, 0u, 0u, 0u};
+            } else if (vec) {  // uniform; N % 8 == 0: the piece lies inside the row
+                ra[i] = *reinterpret_cast<const uint4_t*>(grow[i] + na);
+            } else {
+                uint32_t h[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) h[j] = na + j < N ? (uint32_t)grow[i][na + j] : 0u;
+                ra[i] = uint4_t{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+            }
+        }
+        const uint8_t* wrow = qw + (r0 + (long)nt * MX8_DG_BN) * K;  // uniform: the stage's first row
+        const int left = N - nt * MX8_DG_BN;                         // rows of the stage inside N, >= 1
+        if (left >= MX8_DG_BN) {                                     // uniform
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(wrow + woff[i]);
+                rb[i] = bk_ok ? w : 0u;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int r = bc * 8 + i;
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(wrow + ((uint32_t)min(r, left - 1) * (uint32_t)K + wcol));
+                rb[i] = (bk_ok && r < left) ? w : 0u;
+            }
+        }
+        const int n = nt * MX8_DG_BN + sn;
+        const float s = mx_rebias(ssrc[(long)min(n, N - 1) * KB], eb);
+        rs = (sb_ok && n < N) ? s : 1.0f;
+    };
+    auto store = [&](int buf) {
+        unsigned char* st = lds + buf * MX8_DG_STAGE;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int q = t + 256 * i, row = q >> 3, c16 = q & 7;
+            *reinterpret_cast<uint4_t*>(st + row * MX8_DG_APITCH + c16 * 16) = ra[i];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {  // k pair 2 bd + j of rows 8 bc .. + 7: bytes 2 j, 2 j + 1 of every row's dword
+            const uint32_t sel = j ? 0x07060302u : 0x05040100u;
+            const uint4_t w = {__builtin_amdgcn_perm(rb[1], rb[0], sel), __builtin_amdgcn_perm(rb[3], rb[2], sel),
+                               __builtin_amdgcn_perm(rb[5], rb[4], sel), __builtin_amdgcn_perm(rb[7], rb[6], sel)};
+            *reinterpret_cast<uint4_t*>(st + B_OFF + (bd * 2 + j) * MX8_DG_WPITCH + bc * 16) = w;
+        }
+        reinterpret_cast<float*>(st + S_OFF)[sb * MX8_DG_SPITCH + sn] = rs;
+    };
+
+    float16_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+
+    const int rl = lane & 31, hh = lane >> 5;
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int nt = 0; nt < NT; nt++) {
+        const int buf = nt & 1;
+        if (nt + 1 < NT) load(nt + 1);
+        const unsigned char* st = lds + buf * MX8_DG_STAGE;
+        const unsigned char* bcol = st + B_OFF + (wx * 32 + rl) * MX8_DG_WPITCH + hh * 16;
+        const float* scol = reinterpret_cast<const float*>(st + S_OFF) + (wx * 2 + (rl >> 4)) * MX8_DG_SPITCH + hh * 8;
+#pragma unroll
+        for (int ns = 0; ns < MX8_DG_BN / 16; ns++) {
+            typename F::t a[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+                a[i] = __builtin_bit_cast(typename F::t, *reinterpret_cast<const uint4_t*>(st + (wy * 64 + i * 32 + rl) * MX8_DG_APITCH + ns * 32 + hh * 16));
+            const uint4_t w = *reinterpret_cast<const uint4_t*>(bcol + ns * 32);
+            const float4_t s0 = *reinterpret_cast<const float4_t*>(scol + ns * 16), s1 = *reinterpret_cast<const float4_t*>(scol + ns * 16 + 4);
+            typename F::t b0, b1;  // output columns 2 rl and 2 rl + 1 of the wave's 64
+            mx8_frag_columns<DT>(w, s0, s1, b0, b1);
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                acc[i][0] = F::mfma(a[i], b0, acc[i][0]);
+                acc[i][1] = F::mfma(a[i], b1, acc[i][1]);
+            }
+        }
+        if (nt + 1 < NT) store(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D: lane column rl = output columns k0 + wx 64 + 2 rl (acc[.][0]) and + 1 (acc[.][1]), tile row (r & 3) + 8 (r >> 2) + 4 hh
+    const int k = k0 + wx * 64 + 2 * rl;
+    if (k >= K) return;  // K % 32 == 0 and k is even: the pair lies inside K or outside
+    const float cs = e8m0_f32(eblk[k >> 5]);
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = wy * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (rows.live(row)) mx_store2<ODT>(gx, rows.dst(row) * K + k, acc[i][0][r] * cs, acc[i][1][r] * cs);
+        }
 }
 
 }  // namespace bie
