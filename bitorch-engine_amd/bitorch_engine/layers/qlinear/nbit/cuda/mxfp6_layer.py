@@ -23,6 +23,7 @@ from torch.autograd import Function
 from bitorch_engine.utils.safe_import import import_extension
 from bitorch_engine.utils.model_helper import flatten_x, unflatten_x
 from bitorch_engine.layers.qlinear.ternary.layer import TernaryWeightState
+from bitorch_engine.layers.qlinear.nbit.cuda.mx_grad_weight import GradWeightChoice, weight_grads
 
 mxfp6_linear_cuda = import_extension("mxfp6_linear_cuda")
 
@@ -31,36 +32,34 @@ class MXFP6LinearForward(Function):
     """Forward: the layer kernels.  Backward (straight-through estimator, in fp32, cast to the dtype):
       grad_x      = gy . W            (kernel: mxfp6_linear_cuda.grad_input on the packed weight, e_blk from the scales of this call)
       grad_weight = gy^T . x          (the float latent weight, as if it were W)
-      grad_bias   = sum_m gy"""
+      grad_bias   = sum_m gy          (with wkernel=True both from one call of csrc/mx_wgrad.hip: mx_grad_weight.weight_grads)"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False):
+    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False, wkernel=False):
         ctx.save_for_backward(x, qweight, scales)
-        ctx.kernel = kernel
+        ctx.kernel, ctx.wkernel = kernel, wkernel
         return mxfp6_linear_cuda.forward(x, qweight, scales, bias, e_col)
 
     @staticmethod
     @typing.no_type_check
     def backward(ctx, gy):
         x, qweight, scales = ctx.saved_tensors
-        grad_x = grad_w = grad_b = None
+        grad_x = None
         if ctx.needs_input_grad[0]:
             if ctx.kernel:
                 grad_x = mxfp6_linear_cuda.grad_input(gy, qweight, scales)
             else:
                 grad_x = gy.float().mm(mxfp6_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
-        if ctx.needs_input_grad[1]:
-            grad_w = gy.float().t().mm(x.float()).to(gy.dtype)
-        if ctx.needs_input_grad[2]:
-            grad_b = gy.float().sum(0).to(gy.dtype)
-        return grad_x, grad_w, grad_b, None, None, None, None
+        grad_w, grad_b = weight_grads(gy, x, ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.wkernel)
+        return grad_x, grad_w, grad_b, None, None, None, None, None
 
 
-class MXFP6LinearCuda(TernaryWeightState, nn.Module):
+class MXFP6LinearCuda(GradWeightChoice, TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight), the
     packed codes `qweight` uint8 [N, 3K/4] and E8M0 `scales` uint8 [N, K/32] (buffers), an optional `bias` [N].
     K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16.  grad_input: "torch" (the backward's grad_x from an fp32 image of W) or "kernel" (from
-    the packed weight)."""
+    the packed weight).  grad_weight: "torch" or "kernel" (grad_weight and grad_bias from csrc/mx_wgrad.hip), an attribute of the object
+    only: not a constructor argument, not saved (mx_grad_weight.py)."""
 
     def __init__(self, input_features: int, out_features: int, bias: bool = False, device: torch.device = None,
                  dtype: torch.dtype = torch.float16, grad_input: str = "torch") -> None:
@@ -140,5 +139,6 @@ class MXFP6LinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return unflatten_x(mxfp6_linear_cuda.forward(x2, qweight, scales, self.bias, e_col), lead)
-        out = MXFP6LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel")
+        out = MXFP6LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel",
+                                       self.grad_weight == "kernel")
         return unflatten_x(out, lead)

@@ -12,7 +12,9 @@ Training (train() with the latent weight): re-quantised on every call by the OCP
 backward is the straight-through composition in torch.  Eval: the packed qweight / scales; a forward with grad enabled is
 differentiable in x (and bias).  The attribute grad_input (not a constructor argument, not saved) chooses where grad_x comes from: "torch"
 (the default) builds an fp32 image of W on every backward call; "kernel" takes it from the packed weight in one call
-(csrc/mxfp8_grad.hip, extensions/mxfp8_grad_cuda.py: no image of W is built).  grad_weight and grad_bias are the same in both."""
+(csrc/mxfp8_grad.hip, extensions/mxfp8_grad_cuda.py: no image of W is built).  grad_weight and grad_bias are the same in both.
+The attribute grad_weight (built the same way) chooses where they come from: "torch" (the default) or "kernel" (one call of
+csrc/mx_wgrad.hip through extensions/mx_grad_weight_cuda.py: gy^T . x and the bias sum without an fp32 copy or a torch product)."""
 import math
 import typing
 
@@ -23,6 +25,7 @@ from torch.autograd import Function
 from bitorch_engine.utils.safe_import import import_extension
 from bitorch_engine.utils.model_helper import flatten_x, unflatten_x
 from bitorch_engine.layers.qlinear.ternary.layer import TernaryWeightState
+from bitorch_engine.layers.qlinear.nbit.cuda.mx_grad_weight import GradWeightChoice, weight_grads
 
 mxfp8_linear_cuda = import_extension("mxfp8_linear_cuda")
 mxfp8_grad_cuda = import_extension("mxfp8_grad_cuda")
@@ -38,32 +41,29 @@ class MXFP8LinearForward(Function):
     """Forward: the layer kernels.  Backward (straight-through estimator, in fp32, cast to the dtype):
       grad_x      = gy . W            (W dequantised to fp32; with kernel=True one call of mxfp8_grad_cuda.grad_input on the packed weight)
       grad_weight = gy^T . x          (the float latent weight, as if it were W)
-      grad_bias   = sum_m gy"""
+      grad_bias   = sum_m gy          (with wkernel=True both from one call of csrc/mx_wgrad.hip: mx_grad_weight.weight_grads)"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False):
+    def forward(ctx, x, weight, bias, qweight, scales, e_col, kernel=False, wkernel=False):
         ctx.save_for_backward(x, qweight, scales)
-        ctx.kernel = kernel
+        ctx.kernel, ctx.wkernel = kernel, wkernel
         return mxfp8_linear_cuda.forward(x, qweight, scales, bias, e_col)
 
     @staticmethod
     @typing.no_type_check
     def backward(ctx, gy):
         x, qweight, scales = ctx.saved_tensors
-        grad_x = grad_w = grad_b = None
+        grad_x = None
         if ctx.needs_input_grad[0]:
             if ctx.kernel:
                 grad_x = mxfp8_grad_cuda.grad_input(gy, qweight, scales)
             else:
                 grad_x = gy.float().mm(mxfp8_linear_cuda.dequant(qweight, scales, torch.float32)).to(gy.dtype)
-        if ctx.needs_input_grad[1]:
-            grad_w = gy.float().t().mm(x.float()).to(gy.dtype)
-        if ctx.needs_input_grad[2]:
-            grad_b = gy.float().sum(0).to(gy.dtype)
-        return grad_x, grad_w, grad_b, None, None, None, None
+        grad_w, grad_b = weight_grads(gy, x, ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.wkernel)
+        return grad_x, grad_w, grad_b, None, None, None, None, None
 
 
-class MXFP8LinearCuda(TernaryWeightState, nn.Module):
+class MXFP8LinearCuda(GradWeightChoice, TernaryWeightState, nn.Module):
     """Float latent `weight` [N, K] (kept while training; dropped by generate_quantized_weight(qweight_only=True) or set_mx_weight), the
     e4m3fn codes `qweight` uint8 [N, K] and E8M0 `scales` uint8 [N, K/32] (buffers), an optional `bias` [N].
     K % 32 == 0, 32 <= K <= 2^20; dtype fp16 or bf16.  grad_input: "torch" or "kernel", an attribute of the object only (the module
@@ -162,5 +162,6 @@ class MXFP8LinearCuda(TernaryWeightState, nn.Module):
                                             or (self.bias is not None and self.bias.requires_grad))
         if not grad:
             return unflatten_x(mxfp8_linear_cuda.forward(x2, qweight, scales, self.bias, e_col), lead)
-        out = MXFP8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel")
+        out = MXFP8LinearForward.apply(x2, self.weight if training else None, self.bias, qweight, scales, e_col, self.grad_input == "kernel",
+                                       self.grad_weight == "kernel")
         return unflatten_x(out, lead)

@@ -9,7 +9,8 @@ KNOWN = ("q_linear_cuda", "binary_linear_cpp", "binary_linear_cuda", "binary_lin
          "mxfp4_experts_cuda", "mxfp4_experts_a4_cuda", "mxfp4_a8_linear_cuda", "mxfp4_experts_a8_cuda",
          "mxfp6_a8_linear_cuda", "mxfp6_experts_a8_cuda", "mxfp6_linear_cuda", "mxfp6_experts_cuda",
          "mxfp6_a6_linear_cuda", "mxfp6_experts_a6_cuda", "mxfp4_a6_linear_cuda", "mxfp4_experts_a6_cuda",
-         "mxfp8_a8_linear_cuda", "mxfp8_linear_cuda", "mxfp8_experts_cuda", "mxfp8_grad_cuda")
+         "mxfp8_a8_linear_cuda", "mxfp8_linear_cuda", "mxfp8_experts_cuda", "mxfp8_grad_cuda",
+         "mx_grad_weight_cuda")
 
 
 class ExtensionModulePlaceholder:

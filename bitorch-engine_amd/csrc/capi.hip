@@ -291,6 +291,12 @@ int mxfp8_grad_input_launch(const void* gy, const uint8_t* qw, const uint8_t* sc
                             hipStream_t st);
 int mxfp8_moe_grad_input_launch(const void* gy, const int32_t* idx, const uint8_t* qw, const uint8_t* sc, const uint8_t* eblk, void* gx, void* workspace,
                                 long P, long E, long N, long K, int dtype, int out_fp32, hipStream_t st);
+// mx_wgrad.hip
+long mx_wgrad_max_splits(long M);
+int mx_wgrad_splits(long M, long N, long K);
+size_t mx_wgrad_workspace_bytes(long N, long K, int S);
+int mx_wgrad_launch(const void* gy, const void* x, void* gw, void* gb, void* workspace, long M, long N, long K, int dtype, int out_fp32, int S,
+                    hipStream_t st);
 // intgemm.hip
 int int_gemm_launch(int mode, const void* A, const void* W, void* y, int M, int N, int K, float sa, float sw, int dtype, int batch,
                     long strideA, long strideW, long strideY, hipStream_t st);
@@ -1701,6 +1707,46 @@ int bie_mx8_linear_grad_input(const void* gy, const uint8_t* qweight, const uint
 int bie_mx8_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                            void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream) {
     return mx_w16_moe_grad_input(MX_W8A16, "bie_mx8_moe_grad_input", gy, idx, qweight, scales, e_blk, gx, workspace, T, S, E, N, K, dtype, out_fp32, stream);
+}
+
+// ---- MX weight gradient (gw = gy^T . x, gb = sum_m gy): one kernel for the three weight-only MX layers.  Everything is checked here,
+// before any device call.
+static int check_mx_wgrad(const char* fn, long M, long N, long K) {
+    int rc = check_mx(fn, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(M > 0 && M < (1L << 31) && M * K < (1L << 40) && M * N < (1L << 40), BIE_ERR_INVALID_ARG, "%s: M=%ld (M >= 1 required)", fn, M);
+    return BIE_OK;
+}
+
+// the S of a call: the plan's for -1, else the forced value; 0 where it is out of range
+static long mx_wgrad_resolve(long M, long N, long K, int splits) {
+    if (splits == -1) return mx_wgrad_splits(M, N, K);
+    return splits >= 1 && splits <= mx_wgrad_max_splits(M) ? splits : 0;
+}
+
+int bie_mx_wgrad_splits(long M, long N, long K) { return check_mx_wgrad("bie_mx_wgrad_splits", M, N, K) ? 0 : mx_wgrad_splits(M, N, K); }
+
+size_t bie_mx_wgrad_workspace_bytes(long M, long N, long K, int splits) {
+    if (check_mx_wgrad("bie_mx_wgrad_workspace_bytes", M, N, K)) return 0;
+    return mx_wgrad_workspace_bytes(N, K, (int)mx_wgrad_resolve(M, N, K, splits));
+}
+
+int bie_mx_linear_grad_weight(const void* gy, const void* x, void* gw, void* gb, void* workspace, long M, long N, long K, int dtype, int out_fp32,
+                              int splits, void* stream) {
+    const char* fn = "bie_mx_linear_grad_weight";
+    int rc = check_mx_wgrad(fn, M, N, K);
+    if (rc) return rc;
+    BIE_REQUIRE(dtype == BIE_F16 || dtype == BIE_BF16, BIE_ERR_UNSUPPORTED, "%s: dtype %d (0=f16, 1=bf16)", fn, dtype);
+    BIE_REQUIRE(out_fp32 == 0 || out_fp32 == 1, BIE_ERR_INVALID_ARG, "%s: out_fp32 %d (0 = gw / gb in the dtype, 1 = in fp32)", fn, out_fp32);
+    const long S = mx_wgrad_resolve(M, N, K, splits);
+    BIE_REQUIRE(S >= 1, BIE_ERR_INVALID_ARG, "%s: splits=%d (-1 = the plan, or 1 .. ceil(M / 32) = %ld)", fn, splits, mx_wgrad_max_splits(M));
+    BIE_REQUIRE(((N + 127) / 128) * ((K + 127) / 128) * S < (1L << 31), BIE_ERR_UNSUPPORTED, "%s: N=%ld, K=%ld, splits=%ld beyond the tile count's range", fn,
+                N, K, S);
+    BIE_REQUIRE(gy && x && gw, BIE_ERR_INVALID_ARG, "%s: NULL tensor pointer", fn);
+    BIE_REQUIRE(S == 1 || workspace, BIE_ERR_INVALID_ARG, "%s: splits=%ld needs a workspace of bie_mx_wgrad_workspace_bytes", fn, S);
+    BIE_REQUIRE(!misaligned(gy, 2) && !misaligned(x, 16) && !misaligned(gw, 16) && !misaligned(gb, out_fp32 ? 4 : 2) && !misaligned(workspace, 16),
+                BIE_ERR_INVALID_ARG, "%s: x, gw and workspace must be 16-byte aligned, gy and gb as their elements", fn);
+    return mx_wgrad_launch(gy, x, gw, gb, workspace, M, N, K, dtype, out_fp32, (int)S, as_stream(stream));
 }
 
 // ---- ternary conv2d: the form choice and the two one-launch forms.  Everything is checked here, before any device call.

@@ -1131,6 +1131,29 @@ int bie_mx8_linear_grad_input(const void* gy, const uint8_t* qweight, const uint
 int bie_mx8_moe_grad_input(const void* gy, const int32_t* idx, const uint8_t* qweight, const uint8_t* scales, const uint8_t* e_blk, void* gx,
                            void* workspace, long T, long S, long E, long N, long K, int dtype, int out_fp32, void* stream);
 
+/* ------------------------------------------------------------------------------------------ mx weight gradient
+ * gw = gy^T . x and gb = sum_m gy for the backward of the weight-only MX linear layers (MXFP4LinearCuda, MXFP6LinearCuda,
+ * MXFP8LinearCuda; INTEGRATION.md, "MX weight gradient"): the gradient of the float latent weight, so one entry serves the three formats.
+ *   gw[n, k] = odt( sum_m gy[m, n] * x[m, k] ),  gb[n] = odt( sum_m gy[m, n] );  gy [M, N], x [M, K] in the dtype (0=f16 1=bf16), row-major;
+ *            gw [N, K], gb [N] (NULL = no bias gradient) in the dtype (out_fp32 = 0) or in fp32 (out_fp32 = 1).  Products exact, the sum
+ *            in fp32 in an order fixed by (M, N, K, splits) alone, one rounding.  No atomics: the same arguments give the same bits.
+ *            Non-finite inputs follow IEEE through the products: a NaN in gy[m, n] reaches row n of gw and gb[n] only.
+ *   K % 32 == 0, 32 <= K <= 2^20; any M, N >= 1 (gy rows need no alignment beyond 2 bytes); dtype fp16 or bf16.
+ * One kernel on v_mfma_f32_32x32x16, 128 x 128 tiles of gw, the contraction cut into slabs of 32 rows of M that are staged as they lie
+ * in memory and transposed by the LDS read; no transposed or fp32 copy of gy or x exists.  The slabs are cut into S slices:
+ * S = 1 writes gw / gb directly; S > 1 writes fp32 partials to the workspace and a second kernel adds them in slice order.
+ * bie_mx_wgrad_splits: the plan's S, a function of (M, N, K) alone: the largest S with ceil(N / 128) ceil(K / 128) S <= 512 that
+ *   leaves a slice at least 8 slabs, at least 1 (measured: profiles/mx_wgrad_bench.jsonl).  0 for a refused shape.  Host only.
+ * bie_mx_wgrad_workspace_bytes: S (N K + N) 4 bytes rounded up to 16; 0 for S = 1 or a refused shape or splits.  Host only.
+ * bie_mx_linear_grad_weight: splits -1 = the plan, 1 .. ceil(M / 32) = that many slices, anything else BIE_ERR_INVALID_ARG.  x, gw and
+ *   the workspace (NULL accepted for S = 1; it need not be initialised) 16-byte aligned, gy 2-byte, gb as its elements.  Return codes are
+ *   those of bie_mx8_linear_grad_input; every argument is validated on the host before any device call; nothing allocates or
+ *   synchronises with the host, so the entry can be captured in a graph. */
+int bie_mx_wgrad_splits(long M, long N, long K);
+size_t bie_mx_wgrad_workspace_bytes(long M, long N, long K, int splits);
+int bie_mx_linear_grad_weight(const void* gy, const void* x, void* gw, void* gb, void* workspace, long M, long N, long K, int dtype, int out_fp32,
+                              int splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
